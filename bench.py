@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ensemble DFN trajectory throughput on N MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config C2|C3|C4|C5]
+  python bench.py --gpus 1 --steps K --warmup W [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch = ONE plh_integrate launch that integrates this rank's shard of the ensemble through its whole
@@ -10,8 +10,13 @@ BASELINE.json per GPU ("Batch of 1024 LCO isothermal 1C CC discharges (identical
 contiguous blocks, no data-path collective.  --config selects C3 (4096 thermal cells, CC-CT-CV), C4 (8192 jittered cells per GPU, the shard of the
 65 536-cell sweep) or C5 (1024 NMC + SEI cells, 20 GITT pulses); their inputs are SURVEY.md 8(d)'s (petlion.jl_amd/configs.py).
 
-`value` is the rate with the parameters already resident in HBM (the contract of this benchmark: inputs in HBM when the timed region starts; the host-inclusive
-rate of SURVEY 8(d)'s shape is `host_inclusive` in the same line and is never `value`).  The same JSON line also carries
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, the K timed steps, the result line.  `value` is the rate with the parameters
+already resident in HBM (the contract of this benchmark: inputs in HBM when the timed region starts); `ms_per_step` is the wall time of one timed step.  `roofline` and
+`equivalent_streaming` are arithmetic on the timed region, the device counters of its last step and the committed PMC passes, and stay in every line.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs below); the inputs are a pure function of the arguments, so
+two builds run with the same arguments can be compared array for array.
+--full adds the measurements that take runs of their own (the host-inclusive rate of SURVEY 8(d)'s shape is `host_inclusive` there and is never `value`).
+The JSON line carries
   "roofline":       what actually bounds the kernel -- VALU ISSUE.  The cell state is LDS-resident, one wavefront per SIMD: the kernel moves 0.1 % of the bytes a streaming
                     implementation would, and what a wave spends its life on is issuing fp64 VALU instructions (4 cycles each on the 16-lane fp64 pipe of a gfx950 SIMD).
                     achieved = VALU-busy cycles per second over the launch = (cells x VALU-busy cycles per trajectory, from the committed rocprofv3 PMC pass of THIS binary and
@@ -21,10 +26,11 @@ rate of SURVEY 8(d)'s shape is `host_inclusive` in the same line and is never `v
   "equivalent_streaming": SURVEY.md 8(d)'s algorithmic HBM bytes (byte model x the device counters) / the same kernel duration vs the 8 TB/s HBM3E peak -- the figure r01-r04
                     reported as "roofline".  It prices bytes this kernel never moves (the LDS-resident design exceeds the ceiling a perfect streaming implementation of the
                     north star would have, frac > 1 on C2): kept under its honest name, it bounds nothing;
-  "cpu_baseline":   the oracle (plain-C port of the reference path) on one host core and on all usable cores, bounded sample of the same workload;
-  "host_inclusive": SURVEY 8(d)'s measurement shape -- parameters start in (pinned) host memory, per-cell summaries and sampled outputs end there --
+  --full, "cpu_baseline":   the oracle (plain-C port of the reference path) on one host core and on all usable cores, bounded sample of the same workload;
+  --full, "host_inclusive": SURVEY 8(d)'s measurement shape -- parameters start in (pinned) host memory, per-cell summaries and sampled outputs end there --
                     as a double-buffered PLH_HOST_ASYNC pipeline: median over >= 10 calls;
-  N > 1 only, "ensemble_run": the C4 sweep (8192 cells per GPU) through plh_ensemble_run (RCCL scatter -> integrate -> gather inside the C ABI),
+  --full, "general_path", "with_YP_final", "roofline.measured_copy_peak", and with --config C4 "predicted_scaling": see the functions of those names below;
+  --full, N > 1 only, "ensemble_run": the C4 sweep (8192 cells per GPU) through plh_ensemble_run (RCCL scatter -> integrate -> gather inside the C ABI),
                     block and cyclic partitions, with the per-rank kernel times (load imbalance).
 """
 import argparse
@@ -359,6 +365,37 @@ def general_path(pkg, p, inp, Theta, n_local, kernel_ms, reps=5):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # of the arrays --dump-outputs writes (the files stay well inside 64 MB)
+DUMP_SAMPLE_SEED = 20240         # of the fixed sample of cells taken when the outputs of all cells exceed the budget
+
+
+def dump_outputs(ens, directory):
+    """--dump-outputs: what the last timed step returned to its caller (an EnsembleSolution with device=True, YP not requested), one float64 DIR/<name>.npy per array:
+    t, V, I, SOC (and T_avg with temperature = true) [cell, point], zero beyond the n_pts saved points of a cell (the library leaves that tail unwritten);
+    Y_final [cell, state]; n_pts [cell]; flag, t_end [cell, run] of run_info; n_steps, n_newton [cell] of the counters; cells [cell] = the cell index of every row.
+    All cells when that fits DUMP_BUDGET_BYTES (C2, C5), else a fixed seeded sample of them in ascending order (C3, C4)."""
+    n_pts = ens.n_pts.cpu().numpy().astype(np.int64)
+    n, mp = ens.t.shape
+    names = ["t", "V", "I", "SOC"] + (["T_avg"] if ens.T_avg is not None else [])
+    per_cell = W * (len(names) * mp + ens.Y.shape[1] + 2 * ens.run_info.shape[1] + 4)
+    keep = int(min(n, DUMP_BUDGET_BYTES // per_cell))
+    cells = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+    saved = np.arange(mp)[None, :] < n_pts[cells, None]
+    os.makedirs(directory, exist_ok=True)
+
+    def put(name, a):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    for nm in names:
+        put(nm, np.where(saved, getattr(ens, nm).cpu().numpy()[cells], 0.0))
+    put("Y_final", ens.Y.cpu().numpy()[cells])
+    put("n_pts", n_pts[cells])
+    put("flag", ens.run_info["flag"][cells])
+    put("t_end", ens.run_info["t_end"][cells])
+    put("n_steps", ens.counters["n_steps"][cells])
+    put("n_newton", ens.counters["n_newton"][cells])
+    put("cells", cells)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -367,10 +404,13 @@ def main():
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--cells-per-gpu", type=int, default=0)
     ap.add_argument("--precision", default="f64", choices=("f64", "mixed", "f64_reforder"))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target length of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--leg-timeout", type=int, default=240, help="N > 1: watchdog of the plh_ensemble_run leg (seconds)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-inclusive pipeline, the copy-bandwidth probe and (N > 1) the plh_ensemble_run leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float64; rank 0's shard)")
+    ap.add_argument("--full", action="store_true", help="also run every other measurement: CPU baseline, host-inclusive pipeline, feature costs, YP_final, copy bandwidth, "
+                                                        "(C4) predicted scaling, (N > 1) the plh_ensemble_run leg; --no-cpu-baseline / --no-extras drop parts of it again")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target length of the CPU-baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--leg-timeout", type=int, default=240, help="--full, N > 1: watchdog of the plh_ensemble_run leg (seconds)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the host-inclusive pipeline, the copy-bandwidth probe and (N > 1) the plh_ensemble_run leg")
     args = ap.parse_args()
     c = CONFIGS[args.config]
 
@@ -464,6 +504,8 @@ def main():
         assert (flags[:, 0] == 3).all(), "every C2 cell must end on SOC_min (flag 3), got %r" % np.unique(flags)
         assert np.abs(ens.run_info["t_end"][:, 0] - 3600.0).max() < 1e-5
     bytes_launch = algorithmic_bytes(c, ens.counters, ens.n_pts.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ens, args.dump_outputs)
     kavg_ms = e0.elapsed_time(e1) / args.steps     # average launch duration over the timed region (HIP events on the launch stream)
     klast_ms = float(ens.kernel_ms)                # the library's own event pair around the last launch
     kms = torch.tensor([kavg_ms], dtype=torch.float64, device=cdev)
@@ -521,7 +563,7 @@ def main():
     # ---- N > 1: the C4 sweep through the C ABI's own multi-GPU entry (RCCL scatter -> integrate -> gather), block and cyclic partitions ----
     # The timed region above is complete and `out` holds the line; this extra leg must not be able to lose it: exceptions are caught on every rank (the ranks agree on
     # success through an all_reduce), and a watchdog emits the line without the leg if a collective hangs.
-    if world > 1 and not args.no_extras and backend == "nccl":
+    if args.full and world > 1 and not args.no_extras and backend == "nccl":
         import threading
 
         def give_up():
@@ -575,11 +617,11 @@ def main():
             out["ensemble_run"] = ens_run
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             one, allc = cpu_baseline(args.config, c, p, pkg, inp, args.cpu_seconds)
             out["cpu_baseline"] = one
             out["cpu_baseline_all_cores"] = allc
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["host_inclusive"] = host_inclusive(pkg, p, inp, n_local, kavg_ms)
             out["general_path"] = general_path(pkg, p, inp, Theta, n_local, kavg_ms)
             # like-for-like with r01-r03, whose timed launches also stored YP_final (and with it YP of the previous point at every step): the same workload with YP = True

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The tables of DESIGN.md section 6 / 3 from the bench lines of one GPU call:   python tools/bench_tables.py gpurun_out/r05d   (also writes profiles/r05_bench_lines.json)"""
+"""The tables of DESIGN.md section 6 / 3 from the bench lines of one GPU run, DIR/bench_<config>.json = the line of `python bench.py --full --config <config>`:
+python tools/bench_tables.py DIR [rNN_bench_lines.json]   (the second argument also writes profiles/rNN_bench_lines.json)"""
 import json, os, sys
 d = sys.argv[1]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
