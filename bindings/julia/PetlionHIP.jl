@@ -62,6 +62,7 @@ struct Outputs
     max_pts::Cint; t::Ptr{Cdouble}; V::Ptr{Cdouble}; I::Ptr{Cdouble}; SOC::Ptr{Cdouble}; T_avg::Ptr{Cdouble}
     n_pts::Ptr{Cint}; Y_final::Ptr{Cdouble}; YP_final::Ptr{Cdouble}; run_info::Ptr{RunInfo}; counters::Ptr{Counters}
     Y_all::Ptr{Cdouble}
+    n_sel::Cint; sel::Ptr{Cint}; Y_sel::Ptr{Cdouble}     # selected state ranges per saved point: n_sel pairs (0-based start, len) in host memory, Y_sel[n_sel_total, max_pts, n_cells]
 end
 
 lasterror() = unsafe_string(ccall((:plh_last_error, lib), Cstring, ()))
@@ -206,7 +207,7 @@ end
 the transposed copy is passed).
 """
 function simulate_ensemble(m::Model, p, Θ::Matrix{Float64}, protocol; SOC = p.opts.SOC, max_pts = 2048, Y_init = nothing, t_init = nothing,
-                           outputs = p.opts.outputs, refine = 0)
+                           outputs = p.opts.outputs, refine = 0, sections = ())
     n = size(Θ, 1)
     runs = [make_run(p, s) for s in protocol]
     o = p.opts
@@ -222,16 +223,25 @@ function simulate_ensemble(m::Model, p, Θ::Matrix{Float64}, protocol; SOC = p.o
     keep_Y = any(x -> x ∈ (:all, :Y, :c_e, :c_s_avg, :T, :film, :SOH, :j, :j_s, :Φ_e, :Φ_s), outs)     # solution_states_logic, src/outputs.jl:107-131
     Tavg = p.numerics.temperature ? zeros(max_pts, n) : Float64[]
     Yall = keep_Y ? zeros(m.N, max_pts, n) : Float64[]                  # sol.Y of every cell: Yall[:, k, i] = state after step k of cell i
-    GC.@preserve t V I S npts Y YP info cnt Tavg Yall td ts begin
+    # sections = (:c_e, :T) or 1-based index ranges: only those entries of every saved state vector, packed in the order given (plh_outputs.sel / Y_sel)
+    ind = isempty(sections) ? nothing : state_indices(m)
+    rngs = [x isa Symbol ? ind[x] : x for x in sections]
+    sel = Cint[]; for r in rngs; push!(sel, first(r) - 1, length(r)); end
+    n_selt = sum(length, rngs; init = 0)
+    Ysel = isempty(rngs) ? Float64[] : zeros(n_selt, max_pts, n)       # Ysel[sel_ind[name], k, i]
+    offs = cumsum([0; length.(rngs)])
+    sel_ind = Dict(sections[q] => (offs[q]+1):offs[q+1] for q in eachindex(rngs))
+    GC.@preserve t V I S npts Y YP info cnt Tavg Yall td ts sel Ysel begin
         out = Ref(Outputs(max_pts, pointer(t), pointer(V), pointer(I), pointer(S), isempty(Tavg) ? C_NULL : pointer(Tavg), pointer(npts), pointer(Y), pointer(YP),
-                          pointer(info), pointer(cnt), keep_Y ? pointer(Yall) : C_NULL))
+                          pointer(info), pointer(cnt), keep_Y ? pointer(Yall) : C_NULL,
+                          length(rngs), isempty(rngs) ? C_NULL : pointer(sel), isempty(rngs) ? C_NULL : pointer(Ysel)))
         rc = ccall((:plh_integrate, lib), Cint,
                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Run}, Ref{Opts}, Ref{Outputs}, Cint, Ptr{Cvoid}),
                    m.h, n, Θt, soc, Y_init === nothing ? C_NULL : pointer(Y_init), t_init === nothing ? C_NULL : pointer(t_init),
                    length(runs), runs, opts, out, PLH_HOST, C_NULL)
         check(rc, "plh_integrate")
     end
-    (t = t, V = V, I = I, SOC = S, T_avg = Tavg, Y_all = Yall, n_pts = npts, Y = Y, YP = YP, run_info = info, counters = cnt,
+    (t = t, V = V, I = I, SOC = S, T_avg = Tavg, Y_all = Yall, Y_sel = Ysel, sel_ind = sel_ind, n_pts = npts, Y = Y, YP = YP, run_info = info, counters = cnt,
      flag = [info[end, i].flag for i in 1:n], t_end = [info[end, i].t_end for i in 1:n])
 end
 
@@ -260,7 +270,7 @@ function simulate_ensemble_sens(m::Model, p, Θ::Matrix{Float64}, protocol, keys
     dY = zeros(m.N, ns, n); dV = zeros(max_pts, ns, n); stat = zeros(Cint, 3, n)
     GC.@preserve t V I S npts Y info cnt Tavg ts cols dY dV stat begin
         out = Ref(Outputs(max_pts, pointer(t), pointer(V), pointer(I), pointer(S), isempty(Tavg) ? C_NULL : pointer(Tavg), pointer(npts), pointer(Y), C_NULL,
-                          pointer(info), pointer(cnt), C_NULL))
+                          pointer(info), pointer(cnt), C_NULL, 0, C_NULL, C_NULL))
         rc = ccall((:plh_integrate_sens, lib), Cint,
                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Run}, Ref{Opts}, Ref{Outputs}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
                    m.h, n, Θt, soc, length(runs), runs, opts, out, ns, cols, dY, dV, stat, PLH_HOST, C_NULL)

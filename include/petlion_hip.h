@@ -240,6 +240,18 @@ typedef struct {
   plh_run_info* run_info;            /* [n_cells][n_runs] */
   plh_counters* counters;            /* [n_cells] */
   double* Y_all;                     /* [n_cells][max_pts][N] or NULL: every saved state vector (reference outputs = :all / sol.Y; 2.4 kB per point) */
+  /* Selected state entries per saved point (reference outputs = (:t, :V, :c_e): solution_states_logic, src/outputs.jl:107-131; set_vars!, src/save_outputs.jl:11-40 keep
+     the named states and nothing else).  sel holds n_sel pairs (start, len) of 0-based ranges of the state vector (plh_section gives the named ones), HOST memory like the
+     protocol; the device writes, at exactly the saved points of t / V / ... / Y_all and with the same truncation at max_pts, only those entries, packed in the order
+     given: Y_sel[cell][point][k], n_sel_total = sum of len entries per point, and the row of range i starts at the sum of the lengths before it.  Rules: 0 <= n_sel <= 16;
+     every range has len >= 1 and lies inside [0, N); ranges may come in any order but may not overlap; Y_sel != NULL needs n_sel >= 1.  A violation is PLH_E_ARG (nothing is
+     clamped).  Y_sel and Y_all may both be set: Y_sel then holds the bits of the corresponding columns of Y_all.  These fields are the last of the struct: a caller that
+     zero-initialises plh_outputs gets the behaviour of a library without them.
+     plh_integrate_sens carries Y_sel exactly as it carries Y_all (same saved points).  plh_ensemble_run takes no plh_outputs and returns no per-point array, neither Y_all
+     nor Y_sel. */
+  int n_sel;
+  const int* sel;                    /* [n_sel][2] = (start, len), host memory */
+  double* Y_sel;                     /* [n_cells][max_pts][n_sel_total] or NULL */
 } plh_outputs;
 
 /* ---- model handle: replaces petlion()'s generated-function bundle p.funcs (src/structures.jl:315-334) ---- */

@@ -67,7 +67,8 @@ class CountersS(C.Structure):
 class Outputs(C.Structure):
     _fields_ = [("max_pts", C.c_int), ("t", C.c_void_p), ("V", C.c_void_p), ("I", C.c_void_p), ("SOC", C.c_void_p),
                 ("T_avg", C.c_void_p), ("n_pts", C.c_void_p), ("Y_final", C.c_void_p), ("YP_final", C.c_void_p),
-                ("run_info", C.c_void_p), ("counters", C.c_void_p), ("Y_all", C.c_void_p)]
+                ("run_info", C.c_void_p), ("counters", C.c_void_p), ("Y_all", C.c_void_p),
+                ("n_sel", C.c_int), ("sel", C.POINTER(C.c_int)), ("Y_sel", C.c_void_p)]      # selected state ranges per saved point (plh_outputs.sel: host memory)
 
 
 RUN_INFO_DTYPE = np.dtype([("flag", np.int32), ("iterations", np.int32), ("t_end", np.float64), ("V", np.float64),

@@ -551,6 +551,9 @@ class Solution:
         self.YP = None
         self.T_avg = None      # [points] with temperature = true
         self.Y_all = None      # [points, N] when the run was made with outputs = "all" / a state name (sol.Y of the reference)
+        self.Y_sel = None      # [points, n_sel_total] when the run was made with sections = (...): only the selected state entries, packed in the order given
+        self._sel = None       # the selection as ((start, len), ...) and each of its keys as a slice into a row of Y_sel
+        self._sel_ind = None
         self._ind = None
         self.results = []
         self.counters = None
@@ -563,7 +566,10 @@ class Solution:
         ind = self.__dict__.get("_ind")
         if ind and name in ind:
             if self.__dict__.get("Y_all") is None:
-                raise AttributeError("%s was not saved: run with outputs='all' (or outputs=(%r,))" % (name, name))
+                sel_ind = self.__dict__.get("_sel_ind")
+                if sel_ind and name in sel_ind and self.__dict__.get("Y_sel") is not None:      # saved as a selected section (sections = (name, ...))
+                    return self.Y_sel[:, sel_ind[name]]
+                raise AttributeError("%s was not saved: run with sections=(%r,) or outputs='all'" % (name, name))
             return self.Y_all[:, ind[name]]
         raise AttributeError(name)
 
@@ -593,9 +599,9 @@ class Solution:
         out.t = tq
         out.results = [self.results[i] for i in sorted(set(which.tolist()))]
         out.Y, out.YP, out.counters = self.Y, self.YP, self.counters
-        out._ind = self._ind
+        out._ind, out._sel, out._sel_ind = self._ind, self._sel, self._sel_ind
         start = np.concatenate([[0], np.cumsum([r.iterations for r in self.results])])
-        names = ["V", "I", "SOC", "P"] + (["T_avg"] if self.T_avg is not None else []) + (["Y_all"] if self.Y_all is not None else [])
+        names = ["V", "I", "SOC", "P"] + (["T_avg"] if self.T_avg is not None else []) + (["Y_all"] if self.Y_all is not None else []) + (["Y_sel"] if self.Y_sel is not None else [])
         for name in names:
             x = getattr(self, name)
             y = np.zeros(tq.shape + x.shape[1:])
@@ -652,6 +658,33 @@ def _wants_states(p, outputs):
     return "all" in outs or any(x in _STATE_OUTPUTS for x in outs)
 
 
+def _resolve_sections(p, sections):
+    """sections = names of p.ind and / or (start, len) pairs -> (the selection as a tuple of (start, len), {key: slice into the packed row of Y_sel}); the order given is kept.
+    Only the spelling is checked here: bounds, overlaps and the number of ranges are the library's to refuse (plh_outputs.sel)."""
+    if sections is None:
+        return None, None
+    items = (sections,) if isinstance(sections, str) else tuple(sections)
+    if len(items) == 2 and all(isinstance(x, (int, np.integer)) for x in items):
+        items = (items,)                                               # one bare (start, len) pair
+    if not items:
+        raise ValueError("sections: name at least one state section or (start, len) range")
+    sel, sel_ind, off = [], {}, 0
+    for x in items:
+        if isinstance(x, str):
+            if x not in p.ind:
+                raise ValueError("sections: %r is not a state section of this model (%s)" % (x, ", ".join(p.ind)))
+            a, ln = p.ind[x].start, p.ind[x].stop - p.ind[x].start
+        else:
+            a, ln = (int(v) for v in x)
+            x = (a, ln)
+        if x in sel_ind:
+            raise ValueError("sections: %r is named twice" % (x,))
+        sel.append((a, ln))
+        sel_ind[x] = slice(off, off + ln)
+        off += ln
+    return tuple(sel), sel_ind
+
+
 def calc_SOC(p, Y):
     """calc_SOC(Y, p) (reference src/physics_equations/scalar_residual.jl:95-102): the anode's mean c_s_avg as a fraction of its stoichiometry window"""
     Y = np.asarray(Y, dtype=np.float64)
@@ -660,8 +693,10 @@ def calc_SOC(p, Y):
     return (Y[..., cs.start + n_p:cs.stop].mean(axis=-1) / p.θ["c_max_n"] - p.θ["θ_min_n"]) / (p.θ["θ_max_n"] - p.θ["θ_min_n"])
 
 
-def simulate(p, tf=1e6, *, sol=None, SOC=None, initial_states=None, **kw):
+def simulate(p, tf=1e6, *, sol=None, SOC=None, initial_states=None, sections=None, **kw):
     """simulate(p, tf; I=..|V=..|dT=.., SOC, abstol, reltol, ..., V_max, V_min, ...) for ONE cell (n_cells = 1 ensemble).
+    sections = ("c_e", "T", (start, len), ...): keep only these entries of the state vector per saved point (sol.Y_sel, sol.c_e, sol(t).c_e) instead of the whole vector that
+    outputs = "all" keeps; a continued solution keeps its selection, and continuing it with another one is refused.
     initial_states = Y (reference src/model_evaluation.jl:15, 102-110, 193-199): a new solution that starts from this state vector instead of initial_guess!; its SOC is
     calc_SOC(Y)."""
     inputs, bounds, rest = _split_kwargs(p, kw)
@@ -688,6 +723,11 @@ def simulate(p, tf=1e6, *, sol=None, SOC=None, initial_states=None, **kw):
     new = sol is None or sol.isempty()
     sol = Solution() if sol is None else sol
     keep_Y = _wants_states(p, o.outputs) or sol.Y_all is not None
+    sel, sel_ind = _resolve_sections(p, sections)
+    if not new:
+        if sections is not None and sel != sol._sel:
+            raise ValueError("the solution being continued was saved with sections=%r: a continuation keeps that selection" % (sol._sel,))
+        sel, sel_ind = sol._sel, sol._sel_ind
     soc0 = (p.opts.SOC if SOC is None else SOC) if new else sol.SOC[-1]
     if initial_states is not None:
         soc0 = float(calc_SOC(p, initial_states))                      # (starting_from_initial_state: the estimated SOC, model_evaluation.jl:197-199)
@@ -706,7 +746,7 @@ def simulate(p, tf=1e6, *, sol=None, SOC=None, initial_states=None, **kw):
             initial_states = Y0[0]
     want_Y0 = ss_key is not None and not ss_hit                        # (a miss: the initialised algebraic states are the first saved state vector)
     ens = _integrate(p, p.theta_vector()[None, :], np.array([soc0]), [_make_run(p, name, inp, tf, bounds)], o,
-                     Y_init=(None if initial_states is None else initial_states[None, :]) if new else sol.Y[None, :], t_init=None if new else np.array([sol.t[-1]]), keep_Y=keep_Y or want_Y0)
+                     Y_init=(None if initial_states is None else initial_states[None, :]) if new else sol.Y[None, :], t_init=None if new else np.array([sol.t[-1]]), keep_Y=keep_Y or want_Y0, sections=sel)
     if want_Y0 and int(ens["run_info"][0, 0]["flag"]) >= 0:
         p.save_start_dict[ss_key] = ens["Y_all"][0, 0, p.N.diff:].copy()
     n = int(ens["n_pts"][0])
@@ -725,6 +765,10 @@ def simulate(p, tf=1e6, *, sol=None, SOC=None, initial_states=None, **kw):
         if prev.shape[0] != len(sol.t) - n:
             raise ValueError("the solution being continued was not saved with outputs='all'")
         sol.Y_all = np.concatenate([prev, ens["Y_all"][0, :n]])
+    if sel is not None:
+        prev = sol.Y_sel if sol.Y_sel is not None else np.zeros((0, ens["Y_sel"].shape[2]))
+        sol.Y_sel = np.concatenate([prev, ens["Y_sel"][0, :n]])
+        sol._sel, sol._sel_ind = sel, sel_ind
     sol.Y, sol.YP = ens["Y"][0].copy(), ens["YP"][0].copy()
     t_start = ens["t"][0, 0]
     sol.results.append(RunResult(name, (t_start, ri["t_end"]), ri["flag"], ri["iterations"], ri))
@@ -739,9 +783,10 @@ def simulate_b(sol, p, tf=1e6, **kw):
     return simulate(p, tf, sol=sol, **kw)
 
 
-def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, stream=None, max_points=None, keep_Y=False, keep_YP=True, sens=None):
+def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, stream=None, max_points=None, keep_Y=False, keep_YP=True, sens=None, sections=None):
     """one plh_integrate call; numpy in / numpy out (host pointers) or torch device tensors (device=True).
     keep_YP = False: YP_final is not requested (the reference keeps YP only with var_keep.YP; the kernel then does not store the previous point's YP per step).
+    sections: ((start, len), ...) -> bufs["Y_sel"][cell, point, k]: only those entries of every saved state vector, packed in the order given (plh_outputs.sel / Y_sel).
     sens: list of theta keys -> plh_integrate_sens, bufs["dY_dtheta"][cell, k, state], bufs["dV_dtheta"][cell, k, point], bufs["sens_stat"][cell, 3]."""
     lib, h = p._lib, p._h
     n = theta.shape[0]
@@ -779,6 +824,12 @@ def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, 
     if keep_Y:                          # outputs = :all : every saved state vector
         bufs["Y_all"] = mk(n, mp, N) if device else np.empty((n, mp, N))
         out.Y_all = cap.ptr(bufs["Y_all"])
+    out.n_sel, out.sel, out.Y_sel = 0, None, None
+    if sections is not None:            # selected state entries per saved point
+        sel_arr = np.ascontiguousarray(sections, dtype=np.int32).reshape(-1, 2)
+        n_selt = max(int(sel_arr[:, 1].clip(0).sum()), 1)               # (a selection the library refuses is refused there: the buffer only has to exist)
+        bufs["Y_sel"] = mk(n, mp, n_selt) if device else np.empty((n, mp, n_selt))
+        out.n_sel, out.sel, out.Y_sel = len(sel_arr), sel_arr.ctypes.data_as(C.POINTER(C.c_int)), cap.ptr(bufs["Y_sel"])
     out.n_pts, out.Y_final, out.YP_final = cap.ptr(bufs["n_pts"]), cap.ptr(bufs["Y"]), cap.ptr(bufs["YP"]) if keep_YP else None
     out.run_info, out.counters = cap.ptr(bufs["run_info"]), cap.ptr(bufs["counters"])
     if sens:
@@ -814,13 +865,15 @@ def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, 
 class EnsembleSolution:
     """Per-cell results of an ensemble run (arrays indexed [cell, point]); sol[i] gives a single-cell Solution."""
 
-    def __init__(self, p, bufs, run_names):
+    def __init__(self, p, bufs, run_names, sel=None, sel_ind=None):
         self.p = p
         self.t, self.V, self.I, self.SOC = bufs["t"], bufs["V"], bufs["I"], bufs["SOC"]
         self.n_pts = bufs["n_pts"]
         self.Y, self.YP = bufs["Y"], bufs["YP"]
         self.T_avg = bufs.get("T_avg")          # [cell, point] with temperature = true
         self.Y_all = bufs.get("Y_all")          # [cell, point, state] with outputs = "all"
+        self.Y_sel = bufs.get("Y_sel")          # [cell, point, n_sel_total] with sections = (...): the selected state entries, packed in the order given
+        self.sel, self.sel_ind = sel, sel_ind   # ((start, len), ...) and {name or (start, len): slice into a row of Y_sel}
         self._run_info = bufs["run_info"]
         self._counters = bufs["counters"]
         self.run_names = run_names
@@ -857,6 +910,14 @@ class EnsembleSolution:
     def flags(self):
         return self.run_info["flag"]
 
+    def section(self, name):
+        """[cell, point, len] of one saved state section: from Y_sel when it was selected (sections=), else from Y_all when every state was kept (outputs = "all")"""
+        if self.Y_sel is not None and name in self.sel_ind:
+            return self.Y_sel[:, :, self.sel_ind[name]]
+        if self.Y_all is not None and name in self.p.ind:
+            return self.Y_all[:, :, self.p.ind[name]]
+        raise KeyError("%r was not saved: run with sections=(%r,) or outputs='all'" % (name, name))
+
     def __getitem__(self, i):
         host = lambda x: (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)).copy()      # device=True results are torch tensors in HBM
         s = Solution()
@@ -869,6 +930,8 @@ class EnsembleSolution:
             s.T_avg = host(self.T_avg[i, :n])
         if self.Y_all is not None:
             s.Y_all = host(self.Y_all[i, :n])
+        if self.Y_sel is not None:
+            s.Y_sel, s._sel, s._sel_ind = host(self.Y_sel[i, :n]), self.sel, self.sel_ind
         t0 = 0.0
         for k, nm in enumerate(self.run_names):
             ri = self.run_info[i, k]
@@ -898,12 +961,15 @@ def make_protocol(p, protocol, n_cells=None):
     return runs, names
 
 
-def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, stream=None, max_points=None, outputs=None, YP=True, sens=None, initial_states=None):
+def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, stream=None, max_points=None, outputs=None, YP=True, sens=None, initial_states=None, sections=None):
     """Integrate an ensemble of independent cells on this process's GPU.
 
     Theta: [n_cells, n_theta] array in `p.θ_keys` order (numpy = host memory; torch CUDA tensor with device=True = already in HBM).
     protocol: list of run dicts (see make_protocol) shared by all cells.  SOC: scalar or [n_cells] initial SOC.
     outputs: "all" (or any state name) also returns every saved state vector as ens.Y_all [cell, point, state] -- 8 N bytes per point.
+    sections: ("c_e", "T", (start, len), ...) -- state names of p.ind and / or index ranges: ens.Y_sel [cell, point, n_sel_total] holds only those entries of every saved
+    state vector, packed in the order given (8 n_sel_total bytes per point instead of 8 N); ens.sel_ind[name] is the slice of a section in that row, ens.section(name) the
+    section itself.  Independent of `outputs`: with both, Y_sel repeats the columns of Y_all.
     YP = False: do not return YP of the final point (the reference's default: var_keep.YP is off unless :YP is among the outputs).
     sens = ["D_sp", "k_n", ...]: forward sensitivities with respect to these entries of θ next to the states (plh_integrate_sens): ens.dY_dtheta[cell, k, state] at the
     end of the protocol, ens.dV_dtheta[cell, k, point] at every saved point; the states and saved points are those of the call without `sens`.
@@ -931,9 +997,10 @@ def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, 
             cs = p.ind["c_s_avg"]
             n_p = p.N.p * p.N.r_p if p.solid_diffusion == "Fickian" else p.N.p
             soc0 = np.ascontiguousarray((Y0[:, cs.start + n_p:cs.stop].mean(axis=1) / col("c_max_n") - col("θ_min_n")) / (col("θ_max_n") - col("θ_min_n")))
+    sel, sel_ind = _resolve_sections(p, sections)
     bufs = _integrate(p, Theta, soc0, runs, o, Y_init=Y0, device=device, stream=stream, max_points=max_points,
-                      keep_Y=_wants_states(p, o.outputs if outputs is None else outputs), keep_YP=YP, sens=sens)
-    return EnsembleSolution(p, bufs, names)
+                      keep_Y=_wants_states(p, o.outputs if outputs is None else outputs), keep_YP=YP, sens=sens, sections=sel)
+    return EnsembleSolution(p, bufs, names, sel, sel_ind)
 
 
 def theta_matrix(p, n_cells, overrides=None):
@@ -957,7 +1024,7 @@ class HostPipeline:
             pipe.submit(slot, Theta)
     """
 
-    def __init__(self, p, n_cells, protocol, SOC=1.0, opts=None, max_points=256, depth=2, streams=None):
+    def __init__(self, p, n_cells, protocol, SOC=1.0, opts=None, max_points=256, depth=2, streams=None, sections=None):
         import torch                                                   # streams only (plumbing)
         self.p, self.n, self.depth = p, int(n_cells), int(depth)
         self.runs, self.names = make_protocol(p, protocol, n_cells)
@@ -976,6 +1043,9 @@ class HostPipeline:
             cap.check(lib, lib.plh_host_alloc(C.byref(ptr), nbytes), "plh_host_alloc")
             self._blocks.append(ptr)
             return np.frombuffer((C.c_char * nbytes).from_address(ptr.value), dtype=dt).reshape(shape)
+        # sections = (...): every slot also carries Y_sel [cell, point, n_sel_total] (pinned), see simulate_ensemble; self.sel_ind[name] is a section's slice of the row
+        self.sel, self.sel_ind = _resolve_sections(p, sections)
+        self._sel_arr = None if self.sel is None else np.ascontiguousarray(self.sel, dtype=np.int32).reshape(-1, 2)
         self.slots = []
         for _ in range(self.depth):
             b = dict(theta=pinned((self.n, P), np.float64), soc=pinned((self.n,), np.float64), t=pinned((self.n, self.mp), np.float64), V=pinned((self.n, self.mp), np.float64),
@@ -985,6 +1055,9 @@ class HostPipeline:
             out.max_pts = self.mp
             out.t, out.V, out.n_pts = cap.ptr(b["t"]), cap.ptr(b["V"]), cap.ptr(b["n_pts"])
             out.run_info, out.counters = cap.ptr(b["run_info"]), cap.ptr(b["counters"])
+            if self.sel is not None:
+                b["Y_sel"] = pinned((self.n, self.mp, max(int(self._sel_arr[:, 1].clip(0).sum()), 1)), np.float64)
+                out.n_sel, out.sel, out.Y_sel = len(self._sel_arr), self._sel_arr.ctypes.data_as(C.POINTER(C.c_int)), cap.ptr(b["Y_sel"])
             b["out"] = out
             self.slots.append(b)
 

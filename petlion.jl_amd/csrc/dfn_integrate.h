@@ -960,6 +960,7 @@ PL_DEV void check_stop(CellLDS<M>& S, const plh_run& run, const plh_opts& o, dou
 struct CellOut {
   double *t, *V, *I, *SOC, *T, *Yall;
   int max_pts;
+  double* Ysel; const int* sel_map; int sel_tot;      // plh_outputs.Y_sel: this cell's [max_pts][sel_tot] rows, packed entry -> state index (global memory), entries per row
 };
 
 // the whole protocol for one cell.  Yprev/YPprev: per-cell scratch in HBM.  The back-interpolation of a run that ends on a bound (interp_final_points!) needs the
@@ -1000,6 +1001,13 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
   auto save_pt = [&](int idx, double tt, const double* Y, double soc) {
     const double Tav = (M::THERMAL && out.T) ? cellTavg<M>(S, Y) : T0;
     if constexpr ((F & GF_STOPS) != 0) if (out.Yall && idx < out.max_pts) { PL_VECG(n) out.Yall[(size_t)idx * NST + n] = Y[n]; }      // outputs = :all
+    // selected sections: thread l writes entries l, l + 64, ... of the packed row (contiguous doubles); the entry -> state map is read from global memory at each save (one
+    // coalesced int load per entry, once per accepted step) instead of living in registers across the step loop.  Y is complete for both waves of a two-wave cell here (they
+    // both read V, I and the bounded quantities from it).
+    if constexpr ((F & GF_STOPS) != 0) if (out.Ysel && idx < out.max_pts) {
+      double* const row = out.Ysel + (size_t)idx * out.sel_tot;
+      for (int k = lane + WAVE * wave_id(); k < out.sel_tot; k += WAVE * M::NWAVES) row[k] = Y[out.sel_map[k]];
+    }
     double Vv = cellV<M>(Y), Iv = Y[O_I];                              // (read by every lane AHEAD of the store: no LDS round trip under the lane mask)
     pl_pin(Vv, Iv);
     // r06: lanes 0 .. 4 each own ONE of the five per-point output arrays (pointer in the lane: outp) and store their value with one instruction; r05 had lane 0 walk five

@@ -158,6 +158,8 @@ struct StreamCtx {
   // sorted device copies of opts.tdiscon / opts.tstops, kept per stream (re-uploaded only when they change)
   struct TimeList { double* d = nullptr; int cap = 0; std::vector<double> on_device; };
   TimeList tdiscon, tstops;
+  // packed entry -> state index of plh_outputs.sel (Y_sel), kept per stream like the time lists (re-uploaded only when the selection changes)
+  struct SelMap { int* d = nullptr; int cap = 0; std::vector<int> on_device; } sel;
   hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
   std::vector<hipEvent_t> ret_ev;                           // one event per output array of a synchronous host call (host_return): grown on demand, kept
   std::vector<void*> pending;                               // staging blocks of PLH_HOST_ASYNC launches: released by plh_synchronize
@@ -560,6 +562,7 @@ void plh_model_destroy(plh_model_t m) {
     if (c->d_runs) hipFree(c->d_runs);
     if (c->tdiscon.d) hipFree(c->tdiscon.d);
     if (c->tstops.d) hipFree(c->tstops.d);
+    if (c->sel.d) hipFree(c->sel.d);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->ret_ev) hipEventDestroy(e);
@@ -631,8 +634,9 @@ int plh_abi_layout(int* out, int cap) {
   PL_F(plh_run_info, T_avg)
   PL_S(plh_counters, 11) PL_F(plh_counters, n_steps) PL_F(plh_counters, n_res) PL_F(plh_counters, n_jac) PL_F(plh_counters, n_fact) PL_F(plh_counters, n_solve)
   PL_F(plh_counters, n_newton) PL_F(plh_counters, n_errfail) PL_F(plh_counters, n_convfail) PL_F(plh_counters, sum_kp2) PL_F(plh_counters, n_init_iters) PL_F(plh_counters, cyc)
-  PL_S(plh_outputs, 12) PL_F(plh_outputs, max_pts) PL_F(plh_outputs, t) PL_F(plh_outputs, V) PL_F(plh_outputs, I) PL_F(plh_outputs, SOC) PL_F(plh_outputs, T_avg)
+  PL_S(plh_outputs, 15) PL_F(plh_outputs, max_pts) PL_F(plh_outputs, t) PL_F(plh_outputs, V) PL_F(plh_outputs, I) PL_F(plh_outputs, SOC) PL_F(plh_outputs, T_avg)
   PL_F(plh_outputs, n_pts) PL_F(plh_outputs, Y_final) PL_F(plh_outputs, YP_final) PL_F(plh_outputs, run_info) PL_F(plh_outputs, counters) PL_F(plh_outputs, Y_all)
+  PL_F(plh_outputs, n_sel) PL_F(plh_outputs, sel) PL_F(plh_outputs, Y_sel)
 #undef PL_S
 #undef PL_F
   for (int k = 0; k < (int)v.size() && k < cap; k++) if (out) out[k] = v[k];
@@ -849,6 +853,23 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
     if (runs[r].tf_cell) for (int c = 0; c < n; c++) if (!(runs[r].tf_cell[c] > 0)) return fail(PLH_E_ARG, "run length tf_cell must be positive");
   }
   if (out->max_pts < 0) return fail(PLH_E_ARG, "max_pts");
+  // selected state entries per saved point (plh_outputs.sel / Y_sel): refused, never clamped
+  std::vector<int> sel_map;                                           // packed entry -> state index, in the order the ranges were given
+  if (out->n_sel < 0 || out->n_sel > 16) return fail(PLH_E_ARG, "plh_outputs.n_sel must be 0 .. 16");
+  if (out->n_sel > 0 && !out->sel) return fail(PLH_E_ARG, "plh_outputs.n_sel > 0 needs sel");
+  if (out->Y_sel && out->n_sel == 0) return fail(PLH_E_ARG, "plh_outputs.Y_sel needs n_sel >= 1 ranges in sel");
+  {
+    std::vector<char> taken(m->N, 0);
+    for (int q = 0; q < out->n_sel; q++) {
+      const long long st = out->sel[2 * q], ln = out->sel[2 * q + 1];
+      if (st < 0 || ln < 1 || st + ln > m->N) return fail(PLH_E_ARG, "plh_outputs.sel: every range (start, len) must have len >= 1 and lie inside [0, n_states)");
+      for (long long k = st; k < st + ln; k++) {
+        if (taken[k]) return fail(PLH_E_ARG, "plh_outputs.sel: ranges may not overlap");
+        taken[k] = 1; sel_map.push_back((int)k);
+      }
+    }
+  }
+  const size_t n_selt = out->Y_sel ? sel_map.size() : 0;              // entries per saved row of Y_sel (<= N: the ranges do not overlap)
   if (t_init && !Y_init) return fail(PLH_E_ARG, "t_init without Y_init");        // (Y_init without t_init: a new solution from the caller's states -- initial_states)
   if (opts->n_tdiscon < 0 || (opts->n_tdiscon > 0 && !opts->tdiscon)) return fail(PLH_E_ARG, "tdiscon");
   if (opts->n_tstops < 0 || (opts->n_tstops > 0 && !opts->tstops)) return fail(PLH_E_ARG, "tstops");
@@ -909,6 +930,17 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   };
   if (int rc = time_list(cx.tdiscon, opts->tdiscon, opts->n_tdiscon, &a.opts.tdiscon)) return rc;
   if (int rc = time_list(cx.tstops, opts->tstops, opts->n_tstops, &a.opts.tstops)) return rc;
+  a.sel_map = nullptr; a.sel_tot = (int)n_selt;
+  if (n_selt > 0) {                                                   // the entry -> state map of Y_sel: a device copy kept per stream
+    if (sel_map != cx.sel.on_device) {
+      HIPCHK(hipStreamSynchronize(cx.st));                            // (an earlier launch on this stream may still be reading the old map)
+      if (cx.sel.cap < (int)n_selt) { if (cx.sel.d) hipFree(cx.sel.d); cx.sel.d = nullptr; cx.sel.cap = 0; cx.sel.on_device.clear(); HIPCHK(hipMalloc((void**)&cx.sel.d, (size_t)m->N * sizeof(int))); cx.sel.cap = m->N; }
+      cx.sel.on_device.clear();
+      HIPCHK(hipMemcpy(cx.sel.d, sel_map.data(), n_selt * sizeof(int), hipMemcpyHostToDevice));
+      cx.sel.on_device = sel_map;
+    }
+    a.sel_map = cx.sel.d;
+  }
   // the protocol is always host memory
   if (cx.runs_cap < n_runs) {
     if (cx.d_runs) { HIPCHK(hipStreamSynchronize(cx.st)); hipFree(cx.d_runs); cx.d_runs = nullptr; cx.runs_cap = 0; cx.runs_on_device.clear(); }
@@ -946,6 +978,7 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   a.runs = cx.d_runs;
   const size_t np = (size_t)n * out->max_pts;
   a.out = *out;
+  a.out.n_sel = 0; a.out.sel = nullptr;                               // (host memory: the kernels read a.sel_map / a.sel_tot)
   const bool host_ret = kind == PLH_HOST && !sq;
   // A blocking host call (r06b) keeps its outputs in ONE device block, so that they come back in three copies instead of ten (a device-to-host copy command costs
   // 20 ... 30 us whatever its size): [n_pts] [Y_final, YP_final, run_info, counters] [t, V, I, SOC, T_avg: the requested ones, one [n][max_pts] array behind the other
@@ -953,7 +986,7 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   struct { size_t hdr = 0, npts = 0, fixed0 = 0, fixed1 = 0, pp0 = 0; int n_pp = 0; char* base = nullptr; } lay;          // (hdr: the longest trajectory, worked out on the device)
   if (host_ret) {
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const bool any_pp = np > 0 && (out->t || out->V || out->I || out->SOC || out->T_avg || out->Y_all);
+    const bool any_pp = np > 0 && (out->t || out->V || out->I || out->SOC || out->T_avg || out->Y_all || out->Y_sel);
     size_t off = 0, o_Y = 0, o_YP = 0, o_ri = 0, o_ct = 0;
     lay.hdr = off; off += 256;
     lay.npts = off; if (out->n_pts || any_pp) off += up((size_t)n * sizeof(int));
@@ -974,11 +1007,11 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
       int j = 0;
       for (int k = 0; k < 5; k++) *dst[k] = (*want[k] && np > 0) ? (double*)(lay.base + lay.pp0) + (size_t)(j++) * np : nullptr;
     }
-    a.out.Y_all = s.buf(out->Y_all, np * m->N, false);
+    a.out.Y_all = s.buf(out->Y_all, np * m->N, false); a.out.Y_sel = s.buf(out->Y_sel, np * n_selt, false);
   } else {
     a.out.t = s.buf(out->t, np, false); a.out.V = s.buf(out->V, np, false); a.out.I = s.buf(out->I, np, false);
     a.out.SOC = s.buf(out->SOC, np, false); a.out.T_avg = s.buf(out->T_avg, np, false); a.out.n_pts = s.buf(out->n_pts, n, false);
-    a.out.Y_all = s.buf(out->Y_all, np * m->N, false);
+    a.out.Y_all = s.buf(out->Y_all, np * m->N, false); a.out.Y_sel = s.buf(out->Y_sel, np * n_selt, false);
     a.out.Y_final = s.buf(out->Y_final, (size_t)n * m->N, false); a.out.YP_final = s.buf(out->YP_final, (size_t)n * m->N, false);
     a.out.run_info = s.buf(out->run_info, (size_t)n * n_runs, false); a.out.counters = s.buf(out->counters, n, false);
   }
@@ -1009,7 +1042,7 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   hipEventRecord(cx.ev0, s.st);
   // the instantiation that has the features this call asks for (GenFlag, dfn_integrate.h): 1 = stop times / state dump, 2 = table inputs, 4 = closure inputs, 8 = refinement, 16 = general control row
   int features = 0;
-  if (opts->n_tdiscon > 0 || opts->n_tstops > 0 || out->Y_all || opts->yp_alg_zero != 0) features |= 1;
+  if (opts->n_tdiscon > 0 || opts->n_tstops > 0 || out->Y_all || out->Y_sel || opts->yp_alg_zero != 0) features |= 1;
   for (int r = 0; r < n_runs; r++) { if (runs[r].value_kind == PLH_VAL_TABLE) features |= 1 | 2; if (runs[r].value_kind == PLH_VAL_EXPR) features |= 1 | 2 | 4; }
   if (opts->n_stop > 0) features |= 1 | 2 | 4;                                   // the stop function runs in the interpreter of the closure instantiations
   if (need_genW) features |= 1 | 2 | 4 | 16;                                     // closures with derivative programs: the general control row
@@ -1023,7 +1056,7 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
     // ---- the way back of a synchronous host call (see HostRet and the copy kernels above) ----
     // Items: pieces of the caller's arrays in the order of their arrival.  Every item names the event after which its bytes are in the pinned block; small neighbours share
     // one copy kernel, large arrays are cut into pieces of about 4 MB so that the copy into the caller's memory follows the bus piece by piece.  The pinned block mirrors the
-    // device block ([longest trajectory] [n_pts] [fixed-size arrays] [per-point arrays, each in its worst-case slot, rows packed to the longest trajectory] [Y_all likewise]).
+    // device block ([longest trajectory] [n_pts] [fixed-size arrays] [per-point arrays, each in its worst-case slot, rows packed to the longest trajectory] [Y_all likewise] [Y_sel likewise]).
     struct Item { char* host; size_t rows, width, hpitch, pin_off, elem; int ev; };          // elem != 0: a per-point piece (width and row offsets follow from the longest trajectory)
     std::vector<Item> items;
     std::vector<HostRet> rets;                                          // (for the prefault: the whole arrays)
@@ -1031,7 +1064,8 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
     static const bool trace = getenv("PLH_HOST_TRACE") != nullptr;     // timing of the phases on stderr (tools/gpu: where a blocking call's time goes)
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const size_t yall_bytes = out->Y_all && a.out.Y_all ? np * m->N * W8 : 0, yall0 = (lay.pp0 + (size_t)lay.n_pp * np * W8 + 255) / 256 * 256;
-    const size_t worst = yall0 + yall_bytes + 256;
+    const size_t ysel_bytes = out->Y_sel && a.out.Y_sel ? np * n_selt * W8 : 0, ysel0 = (yall0 + yall_bytes + 255) / 256 * 256;
+    const size_t worst = ysel0 + ysel_bytes + 256;
     const size_t CH = std::max<size_t>(4u << 20, worst / 48);
     char* pb = (char*)m->pinned(worst);
     if (!pb) return fail(PLH_E_HIP, "pinned staging block of the host return path");
@@ -1079,8 +1113,8 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
       flush();
     }
     {                                                                   // the per-point arrays: row pieces sized by the worst case (max_pts columns)
-      struct PP { void* host; const void* dev; size_t elem, slot; } pp[6] = {{out->t, a.out.t, W8, 0}, {out->V, a.out.V, W8, 0}, {out->I, a.out.I, W8, 0}, {out->SOC, a.out.SOC, W8, 0},
-                                                                              {out->T_avg, a.out.T_avg, W8, 0}, {out->Y_all, a.out.Y_all, W8 * m->N, yall0}};
+      struct PP { void* host; const void* dev; size_t elem, slot; } pp[7] = {{out->t, a.out.t, W8, 0}, {out->V, a.out.V, W8, 0}, {out->I, a.out.I, W8, 0}, {out->SOC, a.out.SOC, W8, 0},
+                                                                              {out->T_avg, a.out.T_avg, W8, 0}, {out->Y_all, a.out.Y_all, W8 * m->N, yall0}, {out->Y_sel, a.out.Y_sel, W8 * n_selt, ysel0}};
       size_t slot = lay.pp0;
       for (int k = 0; k < 5; k++) if (pp[k].host && pp[k].dev && mp) { pp[k].slot = slot; slot += np * W8; }
       for (const PP& q : pp) {
@@ -1163,6 +1197,7 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   if ((!plain || sq) && kind != PLH_HOST) HIPCHK(hipStreamSynchronize(s.st));   // staged tables / per-cell values / sensitivity workspaces are released below: the kernel must be done with them
   s.back(out->t, a.out.t, np); s.back(out->V, a.out.V, np); s.back(out->I, a.out.I, np); s.back(out->SOC, a.out.SOC, np);
   s.back(out->T_avg, a.out.T_avg, np); s.back(out->n_pts, a.out.n_pts, n); s.back(out->Y_all, a.out.Y_all, np * m->N);
+  s.back(out->Y_sel, a.out.Y_sel, np * n_selt);
   s.back(out->Y_final, a.out.Y_final, (size_t)n * m->N); s.back(out->YP_final, a.out.YP_final, (size_t)n * m->N);
   s.back(out->run_info, a.out.run_info, (size_t)n * n_runs); s.back(out->counters, a.out.counters, n);
   if (sq) { s.back(sq->dY, a.sens.dY, n_dY); s.back(sq->dV, a.sens.dV, n_dV); s.back(sq->stat, a.sens.stat, (size_t)3 * n); }

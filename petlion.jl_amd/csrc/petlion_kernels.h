@@ -151,6 +151,8 @@ template <class M, int F> __global__ __launch_bounds__(64 * M::NWAVES) PL_ONE_WA
   co.t = a.out.t ? a.out.t + off : nullptr; co.V = a.out.V ? a.out.V + off : nullptr; co.I = a.out.I ? a.out.I + off : nullptr;
   co.SOC = a.out.SOC ? a.out.SOC + off : nullptr; co.T = a.out.T_avg ? a.out.T_avg + off : nullptr;
   co.Yall = a.out.Y_all ? a.out.Y_all + off * NST : nullptr;
+  co.Ysel = nullptr; co.sel_map = nullptr; co.sel_tot = 0;
+  if constexpr ((F & GF_STOPS) != 0) { if (a.out.Y_sel) { co.Ysel = a.out.Y_sel + off * a.sel_tot; co.sel_map = a.sel_map; co.sel_tot = a.sel_tot; } }      // selected entries per saved point
   cell_simulate<F>(S, R, a.tb, a.SOC0[cell], a.Y_init ? a.Y_init + (size_t)cell * NST : nullptr, a.t_init ? a.t_init[cell] : 0.0, a.n_runs, a.runs, a.opts, co, a.out.n_pts ? a.out.n_pts + cell : nullptr,
                 a.out.run_info + (size_t)cell * a.n_runs, cnt,
                 a.out.Y_final ? a.out.Y_final + (size_t)cell * NST : nullptr, a.out.YP_final ? a.out.YP_final + (size_t)cell * NST : nullptr,

@@ -35,6 +35,7 @@ struct IntegrateArgs {
   double* genW;                       // [n_cells][NST] or nullptr: border vector of the general control row (closures with derivative programs)
   pl::SensArgs sens;                  // forward parameter sensitivities (dfn_sens.h); n_sens = 0: none
   double* phig;                       // [n_cells][4][NPAD] or nullptr: BDF history orders 2 .. 5 of the variants that keep them in global memory (ModelT::PHI_GLOBAL)
+  const int* sel_map; int sel_tot;    // out.Y_sel: packed entry k of a saved row is state sel_map[k] ([sel_tot] DEVICE ints built from out.sel, which is host memory and never read by a kernel)
 };
 
 struct SectionInfo { const char* name; int start, len; };
@@ -69,5 +70,5 @@ PL_VARIANT_LIST(PL_DECLARE_OPS)
 extern "C" const VariantOps* plh_grid_variant_ops(int id);     // nullptr: variant not built into this grid library
 extern "C" void plh_grid_dims(int* grid7);
 // what a grid library was compiled against: bump PLH_HOST_ABI whenever VariantOps / IntegrateArgs / Tables change, so that a stale cached library is refused, not misread
-constexpr int PLH_HOST_ABI = 9;
+constexpr int PLH_HOST_ABI = 10;
 extern "C" void plh_grid_abi(int* abi, int* sizeof_ops, int* sizeof_args, int* sizeof_tables);
