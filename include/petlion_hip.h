@@ -231,9 +231,14 @@ typedef struct {
 
 /* outputs of plh_integrate; any pointer may be NULL.  Saved points are the reference's per-step pushes of
  * set_vars! (src/save_outputs.jl:11-40): t = 0 of every run + every accepted step; the last point of a run that ended on
- * a bound is the back-interpolated one (src/model_evaluation.jl:369-382). */
+ * a bound is the back-interpolated one (src/model_evaluation.jl:369-382).
+ * What a blocking PLH_HOST call does to the caller's arrays: an array that is not requested (NULL) is not written.  The per-point arrays (t ... T_avg, Y_all, Y_sel)
+ * receive results only up to the longest trajectory of the call: entries at columns >= max over the cells of n_pts -- like the entries beyond n_pts[cell] of any row,
+ * which no pointer kind defines -- are not copied back.  But the pages of a requested array are touched for the first time while the kernel runs, and that touch may
+ * write ZERO bytes anywhere inside the array before the results arrive: a caller must not expect values it stored in a requested array to survive the call, beyond
+ * the results or not.  (PLH_DEVICE and PLH_HOST_ASYNC write exactly what the kernel writes / copy every requested array back whole.) */
 typedef struct {
-  int max_pts;                       /* row stride of the per-point arrays */
+  int max_pts;                      /* row stride of the per-point arrays */
   double *t, *V, *I, *SOC, *T_avg;   /* [n_cells][max_pts] */
   int* n_pts;                        /* [n_cells] */
   double *Y_final, *YP_final;        /* [n_cells][n_states] */

@@ -93,6 +93,112 @@ def test_three_host_paths_agree(pkg, hip_model_thermal):
     assert np.array_equal(np.asarray(h.T_avg)[0, :int(npd[0])], e.T_avg.cpu().numpy()[0, :int(npd[0])])
 
 
+OPTIONAL = ("t", "V", "I", "SOC", "T_avg", "n_pts", "Y_final", "YP_final", "counters", "Y_all", "Y_sel")
+PER_POINT = ("t", "V", "I", "SOC", "T_avg", "Y_all", "Y_sel")
+
+
+def _three_kinds(pkg, p, Th, proto, soc, mp, want, sel):
+    """one plh_integrate per pointer kind with the arrays of `want` (+ run_info): PLH_DEVICE on torch tensors, a blocking PLH_HOST call with fresh numpy arrays, PLH_HOST_ASYNC
+    through a one-slot HostPipeline whose slot carries pinned arrays for exactly these outputs -> three {name: numpy array}"""
+    import ctypes as C
+    import torch
+    cap, lib = pkg._capi, p._lib
+    n, N = Th.shape[0], p.N.tot
+    sel_arr = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1, 2)
+    runs, _ = pkg.make_protocol(p, proto, n)
+    shapes = dict(t=((n, mp), np.float64), V=((n, mp), np.float64), I=((n, mp), np.float64), SOC=((n, mp), np.float64), T_avg=((n, mp), np.float64),
+                  n_pts=((n,), np.int32), Y_final=((n, N), np.float64), YP_final=((n, N), np.float64), run_info=((n, len(runs)), cap.RUN_INFO_DTYPE),
+                  counters=((n,), cap.COUNTERS_DTYPE), Y_all=((n, mp, N), np.float64), Y_sel=((n, mp, int(sel_arr[:, 1].sum())), np.float64))
+    names = tuple(want) + ("run_info",)
+    nbytes = lambda nm: int(np.prod(shapes[nm][0])) * np.dtype(shapes[nm][1]).itemsize
+
+    def outputs(b):
+        out = cap.Outputs()
+        out.max_pts = mp
+        for nm in names:
+            setattr(out, nm, cap.ptr(b[nm]))
+        out.n_sel, out.sel = len(sel_arr), sel_arr.ctypes.data_as(C.POINTER(C.c_int))
+        return out
+    view = lambda raw, nm: raw.view(shapes[nm][1]).reshape(shapes[nm][0])
+    opts = pkg.api._opts_struct(p.opts, p)
+    arr = (cap.Run * len(runs))(*runs)
+    res = {}
+    # PLH_DEVICE
+    dev = {nm: torch.empty(nbytes(nm), dtype=torch.uint8, device="cuda") for nm in names}
+    Thd, socd = torch.from_numpy(Th).cuda(), torch.full((n,), float(soc), dtype=torch.float64, device="cuda")
+    out = outputs(dev)
+    cap.check(lib, lib.plh_integrate(p._h, n, cap.ptr(Thd), cap.ptr(socd), None, None, len(runs), arr, C.byref(opts), C.byref(out), cap.PLH_DEVICE, None), "PLH_DEVICE")
+    torch.cuda.synchronize()
+    res["PLH_DEVICE"] = {nm: view(dev[nm].cpu().numpy(), nm) for nm in names}
+    # PLH_HOST, arrays no one has touched
+    host = {nm: np.empty(nbytes(nm), np.uint8) for nm in names}
+    out, soch = outputs(host), np.full(n, float(soc))
+    cap.check(lib, lib.plh_integrate(p._h, n, cap.ptr(Th), cap.ptr(soch), None, None, len(runs), arr, C.byref(opts), C.byref(out), cap.PLH_HOST, None), "PLH_HOST")
+    res["PLH_HOST"] = {nm: view(host[nm], nm) for nm in names}
+    # PLH_HOST_ASYNC
+    pipe = pkg.api.HostPipeline(p, n, proto, SOC=soc, max_points=mp, depth=1)
+    try:
+        pin = {}
+        for nm in names:
+            ptr = C.c_void_p()
+            cap.check(lib, lib.plh_host_alloc(C.byref(ptr), nbytes(nm)), "plh_host_alloc")
+            pipe._blocks.append(ptr)                                       # (freed by pipe.close() with the pipeline's own)
+            pin[nm] = np.frombuffer((C.c_char * nbytes(nm)).from_address(ptr.value), dtype=np.uint8)
+        pipe.slots[0]["out"] = outputs(pin)
+        pipe.submit(0, Th)
+        pipe.wait(0)
+        res["PLH_HOST_ASYNC"] = {nm: view(pin[nm].copy(), nm) for nm in names}
+    finally:
+        pipe.close()
+    return res
+
+
+def _same_bits(res, want, n_pts, what):
+    ref = res["PLH_DEVICE"]
+    for kind in ("PLH_HOST", "PLH_HOST_ASYNC"):
+        got = res[kind]
+        assert got["run_info"].tobytes() == ref["run_info"].tobytes(), (what, kind)
+        for nm in want:
+            if nm in PER_POINT:
+                for c in range(len(n_pts)):
+                    k = int(n_pts[c])
+                    assert got[nm][c, :k].tobytes() == ref[nm][c, :k].tobytes(), (what, kind, nm, c)
+            else:
+                assert got[nm].tobytes() == ref[nm].tobytes(), (what, kind, nm)
+
+
+@pytest.mark.parametrize("variant", ["lco_iso", "lco_thermal"])
+def test_output_subsets_agree_across_pointer_kinds(pkg, hip_model, hip_model_thermal, variant):
+    """every requested array holds the same bits whichever way it travels -- everything, run_info alone, everything but n_pts (which the way back of a blocking host call
+    then keeps on the device for itself); 5 cells that differ, 64 points"""
+    p = hip_model if variant == "lco_iso" else hip_model_thermal
+    n, mp = 5, 64
+    Th = np.ascontiguousarray(pkg.configs.sweep_theta(p, np.arange(n), 4))
+    proto = [{"I": -1.0, "tf": 1200.0}]
+    sel = [(p.ind["Φ_e"].start + 3, 7), (p.ind["c_e"].start + 2, 5)]
+    n_pts = None
+    for name, want in (("everything", OPTIONAL), ("only run_info", ()), ("no n_pts", tuple(k for k in OPTIONAL if k != "n_pts"))):
+        res = _three_kinds(pkg, p, Th, proto, 1.0, mp, want, sel)
+        if n_pts is None:
+            n_pts = res["PLH_DEVICE"]["n_pts"].copy()
+            assert 8 <= n_pts.min() and n_pts.max() <= mp and len(set(n_pts.tolist())) > 1, n_pts
+            assert (res["PLH_DEVICE"]["run_info"]["flag"] == 0).all()
+        _same_bits(res, want, n_pts, (variant, name))
+
+
+def test_large_output_block_agrees_across_pointer_kinds(pkg, hip_model):
+    """600 cells with every saved state vector: the output block is far beyond the size at which the way back of a blocking host call starts its team of copying threads
+    and cuts Y_all into pieces (92 MB)"""
+    p = hip_model
+    n, mp = 600, 64
+    Th = np.ascontiguousarray(pkg.configs.sweep_theta(p, np.arange(n), 4))
+    want = ("t", "V", "I", "SOC", "n_pts", "Y_final", "YP_final", "counters", "Y_all")
+    res = _three_kinds(pkg, p, Th, [{"I": -1.0, "tf": 1200.0}], 1.0, mp, want, [(0, 1)])
+    n_pts = res["PLH_DEVICE"]["n_pts"]
+    assert 8 <= n_pts.min() and n_pts.max() <= mp
+    _same_bits(res, want, n_pts, "600 cells, outputs = all")
+
+
 def test_names_follow_the_grid(pkg, hip_model):
     """p.ind of a registered grid library differs from the default grid's: the name -> range mapping of sections= follows the model it is given"""
     import torch
