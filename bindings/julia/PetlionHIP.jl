@@ -279,6 +279,28 @@ function simulate_ensemble_sens(m::Model, p, Θ::Matrix{Float64}, protocol, keys
     (t = t, V = V, I = I, SOC = S, T_avg = Tavg, n_pts = npts, Y = Y, run_info = info, counters = cnt, dY_dθ = dY, dV_dθ = dV, sens_stat = stat)
 end
 
+"""
+    resample(m, ens, field, tq; interp_bc = :interpolate)
+
+`sol(t)` for a whole ensemble (`plh_resample`): the per-point array `field` of `ens = simulate_ensemble(...)` -- `ens.V` (max_pts × n), `ens.Y_all` (N × max_pts × n),
+`ens.Y_sel` ... -- on the time grid `tq` shared by all cells: per run the interpolating cubic spline through its saved points, as the reference's `Spline1D`.
+Returns `(x, status)`: `x` is n_q × n (width × n_q × n for a field with columns); `status[i] = 1` and NaN for a cell that failed or was cut at `max_pts`.
+`interp_bc = :interpolate` holds the first / last saved value of a run outside its points, `:extrapolate` continues the end pieces.
+"""
+function resample(m::Model, ens, field::Array{Float64}, tq::Vector{Float64}; interp_bc = :interpolate)
+    interp_bc ∈ (:interpolate, :extrapolate) || error("Invalid interp_bc method.")
+    max_pts, n = size(ens.t)
+    width = ndims(field) == 3 ? size(field, 1) : 1
+    n_runs = size(ens.run_info, 1)
+    x = ndims(field) == 3 ? zeros(width, length(tq), n) : zeros(length(tq), n)
+    status = zeros(Cint, n)
+    check(ccall((:plh_resample, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{RunInfo}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
+                m.h, n, n_runs, max_pts, ens.t, ens.n_pts, ens.run_info, width, field, length(tq), tq, interp_bc == :extrapolate ? 1 : 0, x, status, PLH_HOST, C_NULL),
+          "plh_resample")
+    (x, status)
+end
+
 # ---- seam 1: the five generated functions of p.funcs (src/structures.jl:315-334) as single-cell evaluators ----
 function residual!(res::Vector{Float64}, m::Model, Y, YP, θ; mode = :I, value = 0.0)
     check(ccall((:plh_residual, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cvoid}),

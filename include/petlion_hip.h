@@ -365,6 +365,26 @@ int plh_last_integrate_compiled(plh_model_t m);
 /* the digest plh_integrate computes for a protocol (0 if it has no PLH_VAL_EXPR run): what a builder embeds in the library */
 unsigned long long plh_closure_digest(int n_runs, const plh_run* runs);
 
+/* ---- the saved points of an ensemble on ONE time grid shared by all cells: the reference's sol(t) / simulate(p, tf::Vector) (src/save_outputs.jl:74-133), which puts an
+ * interpolating spline through each run's saved points (Dierckx Spline1D, s = 0) -- post-interpolation of what plh_integrate wrote, not dense output of the integrator.
+ * Every cell takes its own adaptive steps, so t[cell] differs from cell to cell; this call resamples ONE per-point field per call:
+ *   src[cell][max_pts][width] on the time axis t[cell][max_pts] (V: width 1, Y_all: width N, Y_sel: width n_sel_total), with n_pts / run_info / max_pts as plh_integrate wrote them.
+ * Runs: the saved points of run r of a cell are the rows [start_r, start_r + run_info[cell][r].iterations), start = the running sum of the iterations; run r spans
+ * (t_end of run r-1, t_end of run r), span 0 starts at the cell's first saved time.  A query goes to run 0 when it lies before the first span, else to the first run whose
+ * span holds it (ends included), else to the last run.  A run with n >= 4 points gets the interpolating cubic spline with not-a-knot ends (FITPACK curfit with k = 3, s = 0:
+ * what the reference's Spline1D and scipy's splrep build; equal to it to rounding), n = 3 the parabola, n = 2 the line, n = 1 the constant.
+ * extrapolate = 0 (the reference's interp_bc = :interpolate, bc = "nearest"): a query is clamped to the first / last saved time of its run; 1: the end pieces continue.
+ * What is written: dst[cell][n_q][width], every entry; status[cell] (may be NULL) = 0, or 1 for a cell that cannot be resampled: a run with flag < 0 (PLH_ERR_*,
+ * PLH_ERR_OUTPUT_FULL among them) or without a saved point, or n_pts[cell] != the sum of the runs' iterations (a trajectory cut at max_pts).  Such a cell's dst row is NaN
+ * and none of its points is read.  A NaN query time gives NaN in every cell.  A query at a saved time returns the saved value.
+ * tq[n_q]: solution time, shared by all cells, any order; HOST memory for every ptr_kind (staged like plh_opts.tdiscon).  All other arrays follow ptr_kind: PLH_HOST blocks,
+ * PLH_DEVICE is asynchronous on `stream`.  The slopes live in a per-stream workspace of the handle (max_pts x width doubles per cell) bounded by processing the cells in
+ * chunks: PLH_RESAMPLE_WS_BYTES in the environment (default 256 MiB, read at every call) caps it; the result does not depend on the chunking.
+ * PLH_E_ARG: n_cells, n_runs, max_pts, width or n_q < 1, extrapolate not 0 / 1, a NULL array other than status.  Nothing is clamped. */
+int plh_resample(plh_model_t m, int n_cells, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info,
+                 int width, const double* src, int n_q, const double* tq, int extrapolate,
+                 double* dst /* [n_cells][n_q][width] */, int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

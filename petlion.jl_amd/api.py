@@ -857,9 +857,27 @@ def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, 
                 if hasattr(v, "record_stream"):
                     v.record_stream(ext)
         bufs["kernel_ms"] = lambda: lib.plh_last_kernel_ms(h)     # evaluated on access: the launch is asynchronous on `stream`
+        bufs["stream"] = stream                                   # (what works on these buffers later -- ens(t) -- is queued behind the launch)
     else:
         bufs["kernel_ms"] = lib.plh_last_kernel_ms(h)
     return bufs
+
+
+class ResampledEnsemble:
+    """ens(t): an ensemble's per-point arrays on one time grid (EnsembleSolution.__call__).  t [n_q]; V, I, SOC, T_avg [cell, n_q]; Y_all [cell, n_q, state];
+    Y_sel [cell, n_q, n_sel_total] -- those the ensemble holds and that were asked for, None otherwise; status [cell]."""
+
+    def __init__(self, p, t, sel, sel_ind):
+        self.p, self.t, self.sel, self.sel_ind = p, t, sel, sel_ind
+        self.V = self.I = self.SOC = self.T_avg = self.Y_all = self.Y_sel = self.status = None
+
+    def section(self, name):
+        """[cell, n_q, len] of one state section, as EnsembleSolution.section"""
+        if self.Y_sel is not None and name in self.sel_ind:
+            return self.Y_sel[:, :, self.sel_ind[name]]
+        if self.Y_all is not None and name in self.p.ind:
+            return self.Y_all[:, :, self.p.ind[name]]
+        raise KeyError("%r was not resampled: the ensemble needs sections=(%r,) or outputs='all', and ens(t, fields=...) must include it" % (name, name))
 
 
 class EnsembleSolution:
@@ -875,6 +893,8 @@ class EnsembleSolution:
         self.Y_sel = bufs.get("Y_sel")          # [cell, point, n_sel_total] with sections = (...): the selected state entries, packed in the order given
         self.sel, self.sel_ind = sel, sel_ind   # ((start, len), ...) and {name or (start, len): slice into a row of Y_sel}
         self._run_info = bufs["run_info"]
+        self._run_info_raw = bufs["run_info"]   # as the library wrote it (device=True: stays in HBM, ens(t) hands it back to the library)
+        self._stream = bufs.get("stream")       # device=True: the launch stream
         self._counters = bufs["counters"]
         self.run_names = run_names
         self._kernel_ms = bufs.get("kernel_ms", -1.0)
@@ -917,6 +937,52 @@ class EnsembleSolution:
         if self.Y_all is not None and name in self.p.ind:
             return self.Y_all[:, :, self.p.ind[name]]
         raise KeyError("%r was not saved: run with sections=(%r,) or outputs='all'" % (name, name))
+
+    def __call__(self, t, interp_bc="interpolate", fields=None, k=3):
+        """ens(t): every per-point array of the ensemble (V, I, SOC, T_avg, Y_all, Y_sel -- or only the names in `fields`) on the time grid `t` shared by all cells: the
+        reference's sol(t) (src/save_outputs.jl:74-133) for the whole ensemble, on the device (plh_resample, one call per array; csrc/plh_resample.h).  Per run the interpolating
+        cubic spline through its saved points, the same function as ens[i](t) builds with scipy's splrep to rounding; interp_bc as there.  A device=True ensemble stays in HBM
+        (torch tensors, queued on the launch stream), a host ensemble gives numpy arrays.  Returns a ResampledEnsemble: .t [n_q], the arrays as [cell, n_q(, width)],
+        .status [cell] (1: the cell failed or was cut at max_points -- its rows are NaN), .section(name), .sel_ind."""
+        if k != 3:
+            raise ValueError("ens(t) offers the cubic spline (k = 3) only; another degree: ens[i](t, k=%r), one cell at a time on the host" % (k,))
+        if interp_bc not in ("interpolate", "extrapolate"):
+            raise ValueError("Invalid interp_bc method.")
+        have = [f for f in ("V", "I", "SOC", "T_avg", "Y_all", "Y_sel") if getattr(self, f, None) is not None]
+        names = have if fields is None else [fields] if isinstance(fields, str) else list(fields)
+        for f in names:
+            if f not in have:
+                raise KeyError("%r is not a per-point array of this ensemble (it holds %s)" % (f, ", ".join(have)))
+        tq = np.ascontiguousarray(np.atleast_1d(np.asarray(t, dtype=np.float64)))
+        if tq.ndim != 1 or tq.size < 1:
+            raise ValueError("t must be a time or a 1-D array of times")
+        lib, h = self.p._lib, self.p._h
+        n, mp = self.t.shape
+        device = not isinstance(self.t, np.ndarray)
+        out = ResampledEnsemble(self.p, tq, self.sel, self.sel_ind)
+        if device:
+            import torch
+            dev = self.t.device
+            mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
+            kind, stream, rinfo = cap.PLH_DEVICE, self._stream, self._run_info_raw
+        else:
+            mk = lambda *shape, dt=np.float64: np.empty(shape, dt)
+            kind, stream, rinfo = cap.PLH_HOST, None, np.ascontiguousarray(self.run_info)
+        out.status = mk(n, dt=torch.int32) if device else mk(n, dt=np.int32)
+        made = [out.status]
+        for f in names:
+            x = getattr(self, f)
+            width = 1 if x.ndim == 2 else x.shape[2]
+            y = mk(n, tq.size) if x.ndim == 2 else mk(n, tq.size, width)
+            cap.check(lib, lib.plh_resample(h, n, len(self.run_names), mp, cap.ptr(self.t), cap.ptr(self.n_pts), cap.ptr(rinfo), width, cap.ptr(x), tq.size, tq.ctypes.data,
+                                            1 if interp_bc == "extrapolate" else 0, cap.ptr(y), cap.ptr(out.status), kind, stream), "plh_resample")
+            setattr(out, f, y)
+            made.append(y)
+        if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)      # (allocated on torch's current stream, written on the launch stream: as in _integrate)
+            for v in made:
+                v.record_stream(ext)
+        return out
 
     def __getitem__(self, i):
         host = lambda x: (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)).copy()      # device=True results are torch tensors in HBM

@@ -34,6 +34,8 @@
 #include <rccl/rccl.h>
 #endif
 
+#include "plh_resample.h"
+
 using namespace pl;
 
 static thread_local std::string g_err;
@@ -184,6 +186,8 @@ struct StreamCtx {
   Uploaded<plh_run> runs;                                   // the protocol (remembered when it is plain: a repeated launch with the same protocol uploads nothing and does not synchronise)
   Uploaded<double> tdiscon, tstops;                         // opts.tdiscon / opts.tstops, sorted
   Uploaded<int> sel;                                        // packed entry -> state index of plh_outputs.sel (Y_sel); allocated at N ints, the longest selection there is
+  DevBuf resample;                                          // plh_resample: elimination factors, query locations and slopes of one chunk of cells (plh_resample.h, plrs::Work)
+  Uploaded<double> resample_tq;                             // plh_resample: the query times (remembered: the fields of one ensemble are resampled on the same grid, one call each)
   hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
   std::vector<hipEvent_t> ret_ev;                           // one event per output array of a synchronous host call (host_return): grown on demand, kept
   std::vector<void*> pending;                               // staging blocks of PLH_HOST_ASYNC launches: released by plh_synchronize
@@ -575,7 +579,7 @@ void plh_model_destroy(plh_model_t m) {
   for (void* p : m->d_tables) hipFree(p);
   if (m->d_tb) hipFree(m->d_tb);
   for (StreamCtx* c : m->streams) {
-    for (DevBuf* b : {&c->scratch, &c->genW, &c->phig, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf}) b->free();
+    for (DevBuf* b : {&c->scratch, &c->genW, &c->phig, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf, &c->resample, &c->resample_tq.buf}) b->free();
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->ret_ev) hipEventDestroy(e);
@@ -1217,6 +1221,51 @@ int plh_integrate_sens(plh_model_t m, int n, const double* theta, const double* 
   if (kind != PLH_HOST && kind != PLH_DEVICE) return fail(PLH_E_ARG, "plh_integrate_sens: ptr_kind must be PLH_HOST or PLH_DEVICE");
   const SensReq sq = {n_sens, sens_cols, dY_dtheta, dV_dtheta, sens_stat};
   return integrate_impl(m, n, theta, SOC0, nullptr, nullptr, n_runs, runs, opts, out, kind, stream, &sq);
+}
+
+// ---- plh_resample: one per-point field of an ensemble on a time grid shared by all cells (kernels and algorithm: plh_resample.h) ----
+// The slopes need a workspace of max_pts x width doubles per cell -- a second copy of the field.  It is kept per stream and bounded: the cells are processed in chunks
+// (successive launches on the stream) of at most PLH_RESAMPLE_WS_BYTES of workspace (environment, read at every call; default 256 MiB; never less than one cell).
+int plh_resample(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, int width, const double* src,
+                 int n_q, const double* tq, int extrapolate, double* dst, int* status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1 || n_runs < 1 || max_pts < 1 || width < 1 || n_q < 1) return fail(PLH_E_ARG, "plh_resample: n_cells, n_runs, max_pts, width and n_q must be >= 1");
+  if (!t || !n_pts || !run_info || !src || !tq || !dst) return fail(PLH_E_ARG, "plh_resample: null array (only status may be NULL)");
+  if (extrapolate != 0 && extrapolate != 1) return fail(PLH_E_ARG, "plh_resample: extrapolate must be 0 or 1");
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  StreamCtx& cx = *s.cx;
+  const size_t pts = (size_t)n * max_pts, n_dst = (size_t)n * n_q * width;
+  const double* d_t = s.in(t, pts); const int* d_np = s.in(n_pts, (size_t)n); const plh_run_info* d_ri = s.in(run_info, (size_t)n * n_runs);
+  const double* d_src = s.in(src, pts * width);
+  double* d_dst = s.buf(dst, n_dst, false); int* d_status = s.buf(status, (size_t)n, false);
+  CHECK_STAGE(s);
+  const double* d_tq = nullptr;
+  if (int rc = cx.resample_tq.get(cx.st, std::vector<double>(tq, tq + n_q), &d_tq)) return rc;
+  size_t budget = (size_t)256 << 20;
+  if (const char* e = getenv("PLH_RESAMPLE_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  const size_t per = plrs::work_bytes_per_cell(n_runs, max_pts, n_q, width), n_tiles = ((size_t)width + plrs::TILE - 1) / plrs::TILE;
+  size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
+  chunk = std::max<size_t>(1, std::min(chunk, std::min<size_t>(0x7fffffffu / n_tiles, (size_t)0x7fffffffu * plrs::TILE / (size_t)n_q)));      // (grid sizes of the launches)
+  HIPCHK(cx.resample.reserve(cx.st, chunk * per));
+  plrs::Work w;
+  { char* b = (char*)cx.resample.d;
+    w.fac = (double*)b; b += chunk * max_pts * 2 * sizeof(double);
+    w.loc_t = (double*)b; b += chunk * n_q * sizeof(double);
+    w.slope = (double*)b; b += chunk * max_pts * width * sizeof(double);
+    w.ok = (int*)b; b += chunk * sizeof(int);
+    w.run0 = (int*)b; b += chunk * n_runs * sizeof(int);
+    w.loc_i = (int*)b; }
+  for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+    plrs::Args a;
+    a.cell0 = (int)c0; a.n_chunk = (int)std::min(chunk, (size_t)n - c0);
+    a.n_runs = n_runs; a.max_pts = max_pts; a.width = width; a.n_q = n_q; a.extrapolate = extrapolate;
+    a.t = d_t; a.n_pts = d_np; a.run_info = d_ri; a.src = d_src; a.tq = d_tq; a.dst = d_dst; a.status = d_status; a.w = w;
+    plrs::launch_chunk(s.st, a);
+  }
+  FINISH(s);
+  s.back(dst, d_dst, n_dst); s.back(status, d_status, (size_t)n); CHECK_STAGE(s);
+  return 0;
 }
 
 double plh_last_kernel_ms(plh_model_t m) {
