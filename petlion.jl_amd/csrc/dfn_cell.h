@@ -22,16 +22,11 @@
 
 namespace pl {
 
-// Every device function is inlined into its kernel.  The product build does it late (`inline` here + -mllvm -amdgpu-function-calls=false: the AMDGPU
-// always-inline pass after the function-level optimisations; 0 B of scratch in the isothermal integrate kernel); tools/experiments/build_modes.py also builds
-// "early" (-DPL_DEV='__device__ __forceinline__', no flag) and, through PL_DEV_FACTOR, the thermal factorisation as a real function (-DPL_FACTOR_CALL).
+// Every device function is inlined into its kernel.  WHEN is a row of the flag table (petlion.jl_amd/buildflags.py): the product build does it early
+// (-DPL_DEV='__device__ __forceinline__': merged before the optimisation pipeline); the default below is the late form (`inline` here + -mllvm
+// -amdgpu-function-calls=false: the AMDGPU always-inline pass after the function-level optimisations) that variant 8 and the conservative fall-back set keep.
 #ifndef PL_DEV
 #define PL_DEV __device__ inline
-#endif
-#if defined(PL_FACTOR_CALL) && !defined(PL_WAVE_EMU)
-#define PL_DEV_FACTOR __device__ __attribute__((noinline))
-#else
-#define PL_DEV_FACTOR PL_DEV
 #endif
 
 constexpr int WAVE = 64;
@@ -121,24 +116,12 @@ template <int CHEM_, bool SEI_, bool THERMAL_ = false, int PREC_ = 0, int SD_ = 
   static_assert(PREC_ >= 0 && PREC_ <= 2, "precision");
   using fact_t = typename std::conditional<MIXED, float, double>::type;
   // LDS diet: the error weights and the accumulated Newton correction live in registers (IdaScalars::ew / ee: they are only touched by the
-  // lane-strided vector phases), and so do the BDF history vectors of order >= PHI_LDS
-  // r05, two cells per SIMD (PL_OCC2 builds, tools/experiments/occupancy.py): the isothermal Fickian models (with or without SEI) keep BDF history orders >= 2 in
-  // GLOBAL memory (per-cell block of 4 vectors, lane-strided and coalesced; L2-resident: 6 cells per CU x 9.7 kB) and read the eigen-decomposition of the radial operator from the
-  // model tables at a Jacobian refresh instead of an LDS copy: 37.5 kB -> 26.2 kB per cell, six cells per CU, and the kernels are compiled for two waves per SIMD (256 registers).
-  // -DPL_OCC2=4 (r05, second experiment): only the orders 4 and 5 go to global memory -- they are in use in a minority of the steps at the default tolerances (mean order 2.2 on
-  // C2) -- and everything else stays as it is: 37.5 -> 32.7 kB, FIVE cells per CU (the SIMD that holds two runs both at 256 registers, which costs this kernel nothing: measured).
-#ifdef PL_OCC2
-  static constexpr bool PHI_GLOBAL = !THERMAL_ && SD_ == 0 && W2_ == 0 && PREC_ != PLH_PREC_MIXED && (PL_OCC2 + 0 != 4 || !SEI_);
-  static constexpr int PHI_GLOBAL_FROM = (PL_OCC2 + 0 == 4) ? 4 : 2;          // first history order kept in global memory
-#else
-  static constexpr bool PHI_GLOBAL = false;
-  static constexpr int PHI_GLOBAL_FROM = 2;
-#endif
-  static constexpr bool PHI_GLOBAL_ALL = PHI_GLOBAL && PHI_GLOBAL_FROM == 2;  // the 26 kB layout: also no LDS copy of the eigen-decomposition, no predictor registers
-  static constexpr int PHI_LDS = THERMAL_ ? 2 : (PHI_GLOBAL ? PHI_GLOBAL_FROM : MAXORD + 1);   // thermal: 40.7 kB -> four cells per CU
+  // lane-strided vector phases), and so do the BDF history vectors of order >= PHI_LDS.  (A layout with the higher orders in global memory, for two cells per SIMD, was
+  // measured slower and removed: DESIGN.md 2.)
+  static constexpr int PHI_LDS = THERMAL_ ? 2 : MAXORD + 1;   // thermal: 40.7 kB -> four cells per CU
   // predictor (y, y') of the step kept in registers across the Newton iteration (else re-summed from phi).  SEI models: since r04 -- with MachineLICM off (__graft_entry__.py) the
   // 24 registers are there (C5 24.6 k -> 25.2 k trajectories/s; with MachineLICM on it cost 1 %).  Thermal model: +0.3 %, within the noise of the boxes, left as it was.
-  static constexpr bool PRED_REGS = !THERMAL_ && !PHI_GLOBAL_ALL;      // (the 26 kB layout: 256 registers per lane, the predictor is re-summed)
+  static constexpr bool PRED_REGS = !THERMAL_;
   static constexpr int NB = THERMAL_ ? 4 : 3;        // node block size of the block-Thomas solve: (c_e, Phi_e, Phi_s[, T])
   static constexpr int O_T = N_CECS;
   static constexpr int O_FILM = N_CECS + (THERMAL_ ? NT : 0), O_SOH = O_FILM + NN;
@@ -153,13 +136,9 @@ template <int CHEM_, bool SEI_, bool THERMAL_ = false, int PREC_ = 0, int SD_ = 
   // clears it once; every vector operation maps 0 to 0; residual / solve / global loads only touch the real entries), so that the lane-strided vector phases run WITHOUT a
   // lane mask: the predicated last trip (lanes < 45) put an exec-mask save / branch / restore around its share of every vector statement and split each phase into
   // basic blocks whose LDS loads could not be issued together.  +1.3 kB of LDS per cell (38.8 of the 40.96 kB that four cells per CU allow); the SEI models (322 states:
-  // 62 more entries x 9 vectors) and the thermal ones (at 40.95 kB) do not have the room and keep the mask.  -DPL_NO_VPAD: the r05 layout (A/B builds).
-#ifdef PL_NO_VPAD
-  static constexpr bool VPAD = false;
-#else
-  static constexpr bool VPAD = !SEI_ && !THERMAL_ && W2_ == 0 && !PHI_GLOBAL && NTRIP * WAVE - NST <= 24;
-#endif
-  static constexpr int NPADG = NST + (NST & 1);             // stride of the state-sized vectors kept in GLOBAL memory (sensitivity histories, PHI_GLOBAL block)
+  // 62 more entries x 9 vectors) and the thermal ones (at 40.95 kB) do not have the room and keep the mask.
+  static constexpr bool VPAD = !SEI_ && !THERMAL_ && W2_ == 0 && NTRIP * WAVE - NST <= 24;
+  static constexpr int NPADG = NST + (NST & 1);             // stride of the state-sized vectors kept in GLOBAL memory (sensitivity histories)
   static constexpr int NPAD = VPAD ? NTRIP * WAVE : NPADG;  // length of the LDS state vectors
 };
 using ModelLcoIso = ModelT<PLH_CHEM_LCO_LIC6, false>;
@@ -300,7 +279,7 @@ template <class M> struct alignas(16) CellLDS {
   // its eigen-decomposition (copies of Tables::V, W, LAM): the resolvents are rebuilt from them at every Jacobian refresh, and reading the tables from HBM there cost
   // 9.7 k cycles per refresh (two dependent rounds of global / scalar loads); from LDS, with the 2 N_r^2 entries spread over the wave, 1 k
   // (one array, so that the models without it -- thermal: 40 952 of the 40 960 B that four cells per CU allow -- pay 8 bytes, not 32)
-  static constexpr int MR_BLK = M::PHI_GLOBAL_ALL ? NR * NR : (M::THERMAL ? 3 * NR * NR : 3 * NR * NR + NR);   // (thermal: M, V, W; the eigenvalues are only read at a factorisation; PHI_GLOBAL: M only)
+  static constexpr int MR_BLK = M::THERMAL ? 3 * NR * NR : 3 * NR * NR + NR;   // (thermal: M, V, W; the eigenvalues are only read at a factorisation)
   alignas(16) double Mr[M::SD != 0 ? 1 : (NR_EQ ? 1 : 2) * MR_BLK];                          // (N_r_p != N_r_n: the cathode's block, then the anode's, both at stride NR, zero-padded)
   static constexpr int OFF_VR = NR * NR, OFF_WR = 2 * NR * NR, OFF_LAMR = 3 * NR * NR;
   static __host__ __device__ constexpr int mr_el(int el) { return NR_EQ ? 0 : el * MR_BLK; }  // offset of electrode el's block
@@ -354,47 +333,7 @@ struct SensArgs {               // (device pointers; part of IntegrateArgs)
 };
 constexpr int SENS_CBAK = 384;
 
-// An index the compiler must treat as opaque: `base + PL_OPAQUE_IDX(lane part)` keeps the lane-dependent part of an LDS address in ONE register and leaves the compile-time part to
-// the instruction's offset field.  Without it the constant parts of S.<array>[lane part + const] are folded into one large immediate per access, which ds_read2_b64's 8-bit
-// offsets cannot hold: the compiler then materialises a separate address (v_add / v_mad) for every pair of loads -- a quarter of the instructions of the particle phases.
-#ifdef PL_WAVE_EMU
-#define PL_OPAQUE_IDX(i) (i)
-typedef const double* lds_cptr;
-typedef double* lds_ptr;
-#define PL_LDS_BASE(p) (p)
-#define PL_LDS_BASE_A(A16, p) (p)
-#else
-__device__ __forceinline__ int pl_opaque_idx(int i) { __asm__("" : "+v"(i)); return i; }
-#define PL_OPAQUE_IDX(i) pl_opaque_idx(i)
-// The same for a whole LDS address: a 32-bit LDS pointer (address_space(3)) the compiler may not look into.  Accesses q[compile-time index] then use q's register plus
-// the instruction's offset field -- within the reach of ds_read2_b64 (2040 B) as long as the indices stay below 256.
-typedef const __attribute__((address_space(3))) double* lds_cptr;
-typedef __attribute__((address_space(3))) double* lds_ptr;
-__device__ __forceinline__ lds_cptr pl_lds_base(const double* p) { lds_cptr q = (lds_cptr)p; __asm__("" : "+v"(q)); return q; }
-__device__ __forceinline__ lds_ptr pl_lds_base(double* p) { lds_ptr q = (lds_ptr)p; __asm__("" : "+v"(q)); return q; }
-#define PL_LDS_BASE(p) pl_lds_base(p)
-// the same for an address the CALLER knows to be 16-byte aligned (A16 true; the asm hides that from the compiler): pairs q[2k], q[2k+1] then load as one ds_read_b128
-template <bool A16> __device__ __forceinline__ lds_cptr pl_lds_base_a(const double* p) { lds_cptr q = pl_lds_base(p); if constexpr (A16) __builtin_assume(((unsigned)(__UINTPTR_TYPE__)q & 15u) == 0u); return q; }
-#define PL_LDS_BASE_A(A16, p) pl_lds_base_a<A16>(p)
-#endif
-
-// lane_id_pred(): the lane number for code whose use of it is PREDICATES (which control volume, which section, first / last of an electrode, node of the twisted layout):
-// its own copy per call site, so that the compares are made where they are used (one v_cmp each) instead of once at the top of the kernel -- where every lane predicate of
-// every inlined phase then lives in an SGPR pair across the whole step loop, i.e. in a spill lane of a VGPR (v_writelane / two v_readlane per use: r05 code object, 1 036 of them)
-// (-DPL_LANE_OPAQUE=0: off; =1: every lane_id(), including the particle phases' lane / N_r arithmetic)
-#ifndef PL_LANE_OPAQUE
-#define PL_LANE_OPAQUE 0
-#endif
-#if PL_LANE_OPAQUE + 0 == 1 && !defined(PL_WAVE_EMU)
-__device__ __forceinline__ int lane_id() { int i = (int)threadIdx.x & (WAVE - 1); __asm__ volatile("" : "+v"(i)); return i; }
-#else
 __device__ __forceinline__ int lane_id() { return (int)threadIdx.x & (WAVE - 1); }
-#endif
-#if PL_LANE_OPAQUE + 0 >= 1 && !defined(PL_WAVE_EMU)
-__device__ __forceinline__ int lane_id_pred() { int i = (int)threadIdx.x & (WAVE - 1); __asm__ volatile("" : "+v"(i)); return i; }
-#else
-__device__ __forceinline__ int lane_id_pred() { return (int)threadIdx.x & (WAVE - 1); }
-#endif
 __device__ __forceinline__ int wave_id() { return (int)threadIdx.x >> 6; }     // 0 for the one-wave kernels; 0 / 1 for M::W2
 
 // Phase separator between LDS producers and consumers.  A workgroup here is exactly ONE wavefront, and the LDS instructions of one
@@ -649,16 +588,7 @@ template <int N> __device__ __forceinline__ void csd_settle(double (&c)[N]) {
 template <int K, int NK, class F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (K < NK) { f(std::integral_constant<int, K>{}); static_for<K + 1, NK>(f); }
 }
-#ifdef PL_NO_CSDPP
-template <class M> constexpr bool PL_CSDPP = false;
-#else
-template <class M> constexpr bool PL_CSDPP = M::SD == 0 && !M::THERMAL && !M::W2;
-#endif
-#ifdef PL_NO_THROWB
-constexpr bool PL_THROWB = false;
-#else
-constexpr bool PL_THROWB = true;          // the thermal model's particle phases in the row layout (dfn_thermal.h)
-#endif
+template <class M> constexpr bool PL_CSDPP = M::SD == 0 && !M::THERMAL && !M::W2;      // (the thermal model's particle phases are always in the row layout: dfn_thermal.h)
 
 // a value the compiler must materialise: a product passed through it is ROUNDED before it enters a sum (no fma contraction) -- the reference's operation order of the
 // PLH_PREC_F64_REFORDER variants (Julia does not contract a*b + c; neither does the oracle's gcc build for x86-64)
@@ -886,7 +816,7 @@ template <class M, bool INIT = true> PL_DEV void thermal_setup(CellLDS<M>& S, co
 template <bool WANT_RES, bool WANT_JAC, class M>
 PL_DEV void thermal_node_pass(CellLDS<M>& S, const double* Y, const double* YP, double* Fo, int mode, double value);
 template <bool WANT_JAC, class M> PL_DEV void thermal_cs_rows(CellLDS<M>& S, const Tables* __restrict__ tb, const double* Y, const double* YP, double* Fo);
-template <class M> PL_DEV_FACTOR void thermal_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb, double cj, int mode, bool alg_only);
+template <class M> PL_DEV void thermal_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb, double cj, int mode, bool alg_only);
 template <class M> PL_DEV void thermal_solve(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb, double* b, int mode, bool alg_only);
 template <bool FROZEN = false, class M> PL_DEV double thermal_jac_entry(const CellLDS<M>& S, const Tables* __restrict__ tb, unsigned w, double cj);
 constexpr int PL_MODE_DT_TWIN = 16;   // dT control row with YP_T replaced by rhs_T(Y): the consistent-initialisation form (scalar_residual.jl:347-372)
@@ -1003,15 +933,12 @@ PL_DEV void cell_setup(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb
   }
   if constexpr (INIT) {
   if constexpr (M::SD == 0) { if (wave_id() == M::NWAVES - 1) {
-    if constexpr (M::PHI_GLOBAL_ALL) {                      // M only: V, W, LAM are read from the tables at a factorisation (iso_factor)
-      for (int k = lane; k < NR * NR; k += WAVE) { S.Mr[k] = tb->Mp()[k]; S.Ainv[0][k] = 0.0; S.Ainv[1][k] = 0.0; if constexpr (!NR_EQ) S.Mr[S.mr_el(1) + k] = tb->Mp(1)[k]; }
-    } else {
     for (int k = lane; k < NR * NR; k += WAVE) { S.Mr[k] = tb->Mp()[k]; S.Mr[S.OFF_VR + k] = tb->Vp()[k]; S.Mr[S.OFF_WR + k] = tb->Wp()[k]; if constexpr (!M::THERMAL) { S.Ainv[0][k] = 0.0; S.Ainv[1][k] = 0.0; } }
     if constexpr (!M::THERMAL) { if (lane < NR) S.Mr[S.OFF_LAMR + lane] = tb->LAMp()[lane]; }
     if constexpr (!NR_EQ) {                                 // the anode's block (the tables are already zero-padded to the common stride: plh_model_create)
       for (int k = lane; k < NR * NR; k += WAVE) { S.Mr[S.mr_el(1) + k] = tb->Mp(1)[k]; S.Mr[S.mr_el(1) + S.OFF_VR + k] = tb->Vp(1)[k]; S.Mr[S.mr_el(1) + S.OFF_WR + k] = tb->Wp(1)[k]; }
       if constexpr (!M::THERMAL) { if (lane < NR) S.Mr[S.mr_el(1) + S.OFF_LAMR + lane] = tb->LAMp(1)[lane]; }
-    } }
+    }
     } }
   for (int k = 0; k < LR_PASS; k++) { R.wreg[k] = 0.0; R.rcp[k] = 0.0; }
   // the LDS state vectors start at zero, padding included: the padding of M::VPAD must be (and then stays) zero, and the branch-free history sums of the integrator multiply
@@ -1058,7 +985,7 @@ template <bool WANT_RES, bool WANT_JAC, class M>
 PL_DEV void iso_node_pass(CellLDS<M>& S, const double* Y, const double* YP, double* Fo, int mode, double value) {
   PL_MODEL(M);
   if constexpr (M::W2) { if (wave_id() != 0) return; }       // two waves per cell: the finite-volume rows belong to wave 0
-  const int lane = lane_id_pred();
+  const int lane = lane_id();
   const CellConst& c = S.cc;
   const int i = lane < NE ? lane : NE - 1;
   const bool act = lane < NE;
@@ -1478,7 +1405,7 @@ __device__ __forceinline__ double u22_of(int n) { return (n < NE - 1 && sec_of(n
 template <class M>
 __device__ __forceinline__ void thomas_sweeps(const CellLDS<M>& S, bool alg_only, double& r0, double& r1, double& r2) {
   PL_MODEL(M);
-  const int lane = lane_id_pred();
+  const int lane = lane_id();
   const int nd = tw_node(lane);
   const bool act = nd >= 0, top = lane < TW_MID;
   const int i = act ? nd : 0;
@@ -1507,11 +1434,7 @@ __device__ __forceinline__ void thomas_sweeps(const CellLDS<M>& S, bool alg_only
   // -- the odd and the even nodes of a half then advance together, two lanes apart (row_shr:2 / row_shl:2: each half of the twisted layout sits inside one 16-lane DPP row), in
   // ceil(n/2) stages.  The products C_n C_{n-1} and the shifted right-hand sides cost one parallel pre-pass (27 + 9 FMAs); they depend on the factors only, but there is no LDS left to
   // keep them in.  (Grids whose halves do not fit a DPP row keep the one-lane recurrence.)
-#ifdef PL_EXP_NO_STRIDE2      /* (experiment build: the one-lane recurrence, for same-box A/B runs) */
-  constexpr bool STRIDE2 = false;
-#else
   constexpr bool STRIDE2 = TW_FWD <= 15 && TW_MID <= 15;
-#endif
   double y0, y1, y2;
   if constexpr (STRIDE2) {
     double P[9];
@@ -1591,8 +1514,7 @@ PL_DEV void iso_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb
   if (!alg_only && (!M::W2 || wave_id() == 1)) {          // (two waves per cell: the resolvents are wave 1's, next to wave 0's Jacobian node pass)
     const int r = lane % NR;
     // the 2 N_r reciprocals 1/(kappa lam_m - cj) are formed by 2 N_r lanes in parallel and passed through S.w9 (free outside the solves)
-    if constexpr (M::PHI_GLOBAL_ALL) { if (lane < 2 * NR) S.w9[lane] = pl_rcp((lane < NR ? c.kap_p : c.kap_n) * tb->LAMp(lane < NR ? 0 : 1)[r] - cj); }
-    else if constexpr (NR_EQ) { if (lane < 2 * NR) S.w9[lane] = pl_rcp((lane < NR ? c.kap_p : c.kap_n) * S.Mr[S.OFF_LAMR + r] - cj); }
+    if constexpr (NR_EQ) { if (lane < 2 * NR) S.w9[lane] = pl_rcp((lane < NR ? c.kap_p : c.kap_n) * S.Mr[S.OFF_LAMR + r] - cj); }
     else { if (lane < 2 * NR) S.w9[lane] = pl_rcp((lane < NR ? c.kap_p : c.kap_n) * S.Mr[(lane < NR ? 0 : S.MR_BLK) + S.OFF_LAMR + r] - cj); }      // (padded modes: lam = 0, V = W = 0)
     PL_SYNC();
     // entry (row, k) of electrode el = sum_m V[row][m] w_el[m] W[m][k], m ascending; lanes 0..31 build the cathode's resolvent, 32..63 the anode's, RS_KG lanes per row with
@@ -1603,11 +1525,7 @@ PL_DEV void iso_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb
     double acc[RS_KW];
     for (int kk = 0; kk < RS_KW; kk++) acc[kk] = 0.0;
     _Pragma("unroll 2") for (int m = 0; m < NR; m++) {            // (fully unrolled, the 60 operands of the sums are all live at once: 132 B/lane of scratch in the integrate kernel)
-      if constexpr (M::PHI_GLOBAL_ALL) {                        // (the same sums in the same order; operands from the model tables: L2 hits, once per Jacobian refresh)
-        const double* __restrict__ Vt = tb->Vp(el); const double* __restrict__ Wt = tb->Wp(el);
-        const double f = Vt[row * NR + m] * S.w9[el * NR + m];
-        for (int kk = 0; kk < RS_KW; kk++) acc[kk] += f * Wt[m * NR + (k0 + kk < NR ? k0 + kk : NR - 1)];
-      } else if constexpr (NR_EQ) {
+      if constexpr (NR_EQ) {
         const double f = S.Mr[S.OFF_VR + row * NR + m] * S.w9[el * NR + m];
         for (int kk = 0; kk < RS_KW; kk++) acc[kk] += f * S.Mr[S.OFF_WR + m * NR + (k0 + kk < NR ? k0 + kk : NR - 1)];
       } else {
@@ -1823,7 +1741,7 @@ PL_DEV void iso_solve(CellLDS<M>& S, LaneRegs& R, double* b, int mode, bool alg_
   double bjp = 0.0, bjs = 0.0, bfl = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0;
   [[maybe_unused]] double bca = 0.0, bq = 0.0;       // right-hand sides of the c_avg / Q rows of this node (quadratic / polynomial particles)
   int jx = 0; bool elec = false, sei_node = false;
-  const int nd = tw_node(lane_id_pred());       // node of this lane in the twisted layout of thomas_sweeps (-1: idle)
+  const int nd = tw_node(lane_id());       // node of this lane in the twisted layout of thomas_sweeps (-1: idle)
   if constexpr (M::SD == 0 && !M::SEI) {       // (measured: +1.5 % on the isothermal kernels, -2 % with SEI, whose integrate kernel is already spilling: selected per model)
     // every LDS operand of this phase is loaded unconditionally, with indices clamped into range for the lanes / nodes that do not use it, and selected afterwards:
     // loads under the nested `if`s (node lane? electrode node? current mode?) were three dependent LDS round trips

@@ -25,7 +25,6 @@ struct IdaScalars {   // the coefficient arrays psi/alpha/beta/sigma/gamma live 
   double pa[NTRIP_MAX], pb[NTRIP_MAX];   // predictor y_n(0), y'_n(0) of the step (models with M::PRED_REGS)   // per-lane entries of the BDF history vectors that are not kept in LDS (models with M::PHI_LDS < 6): [j - PHI_LDS][trip]
   int kk, kused, knew, phase, ns, maxord;
   int nst;
-  double* phg;               // models with M::PHI_GLOBAL: this cell's block of BDF history orders 2 .. 5 in global memory, [4][NPAD], entry n of a vector in lane n % 64
 };
 
 // Feature flags of the integrate kernel's instantiations.  The step loop keeps ~60 per-lane values live next to the cell's LDS block, and code that is merely PRESENT in it costs
@@ -48,16 +47,14 @@ __device__ __forceinline__ void cnt_add(Counters& c, int k, int v = 1) { c.v[k] 
 // lane-strided sweep over the N state entries: exactly 5 trips (301 = 4*64 + 45), fully unrolled so that the LDS loads of all
 // trips are issued back to back (one latency instead of five); only the last trip is predicated.
 // BDF history access inside a PL_VEC loop (k__ = compile-time trip index): vectors j < M::PHI_LDS are LDS arrays, the rest registers in I.ph
-#define PHI_RD(j, n) (M::PHI_GLOBAL ? ((j) < M::PHI_LDS ? S.phi[(j) < M::PHI_LDS ? (j) : 0][n] : I.phg[((j) - M::PHI_LDS) * M::NPADG + (n)]) : PHI_RD_R(j, n))
-#define PHI_WR(j, n, v) do { if constexpr (M::PHI_GLOBAL) { if ((j) < M::PHI_LDS) S.phi[(j) < M::PHI_LDS ? (j) : 0][n] = (v); else I.phg[((j) - M::PHI_LDS) * M::NPADG + (n)] = (v); } else PHI_WR_R(j, n, v); } while (0)
-#define PHI_RD_R(j, n) ((M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? S.phi[(M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? (j) : 0][n] : ((j) == M::PHI_LDS ? I.ph[0][k__] : ((j) == M::PHI_LDS + 1 ? I.ph[1][k__] : ((j) == M::PHI_LDS + 2 ? I.ph[2][k__] : I.ph[3][k__]))))
-#define PHI_WR_R(j, n, v) do { if (M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) S.phi[(M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? (j) : 0][n] = (v); \
-                             else if ((j) == M::PHI_LDS) I.ph[0][k__] = (v); else if ((j) == M::PHI_LDS + 1) I.ph[1][k__] = (v); \
-                             else if ((j) == M::PHI_LDS + 2) I.ph[2][k__] = (v); else I.ph[3][k__] = (v); } while (0)
+#define PHI_RD(j, n) ((M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? S.phi[(M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? (j) : 0][n] : ((j) == M::PHI_LDS ? I.ph[0][k__] : ((j) == M::PHI_LDS + 1 ? I.ph[1][k__] : ((j) == M::PHI_LDS + 2 ? I.ph[2][k__] : I.ph[3][k__]))))
+#define PHI_WR(j, n, v) do { if (M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) S.phi[(M::PHI_LDS > MAXORD || (j) < M::PHI_LDS) ? (j) : 0][n] = (v); \
+                           else if ((j) == M::PHI_LDS) I.ph[0][k__] = (v); else if ((j) == M::PHI_LDS + 1) I.ph[1][k__] = (v); \
+                           else if ((j) == M::PHI_LDS + 2) I.ph[2][k__] = (v); else I.ph[3][k__] = (v); } while (0)
 // accumulated correction ee inside a PL_VEC loop
 #define EE(n) I.ee[k__]
 // some BDF history orders live in registers (thermal model): the step-control passes then index the history with compile-time orders under wave-uniform branches
-template <class M> constexpr bool PHI_REGS = M::PHI_LDS <= MAXORD && !M::PHI_GLOBAL;      // (history in global memory: a runtime order is just an address, as with the whole history in LDS)
+template <class M> constexpr bool PHI_REGS = M::PHI_LDS <= MAXORD;
 #ifdef PL_EXP_BRANCHY_PHI
 constexpr bool PL_BRANCHY_PHI = true;
 #else
@@ -68,12 +65,8 @@ constexpr bool PL_BRANCHY_PHI = false;
 // register-resident orders of the thermal model, r03), orders 4 and 5 under ONE wave-uniform branch, every load of a pass is issued before its arithmetic and the stores follow
 // at the end.  r05's form had a branch per order (and, inside the error test, per trip): each arm waited for its own LDS round trip, and with one wavefront per SIMD nothing
 // hides that -- the phase timers charged 2.2 k cycles per Newton iteration to the iterate / norm passes and 3.6 k per step to IDACompleteStep.  Cells are zero-initialised
-// (cell_setup) so that an order that has never been written is finite.  -DPL_NO_FLAT: the r05 form (A/B builds).
-#ifdef PL_NO_FLAT
-template <class M> constexpr bool PL_FLAT = false;
-#else
-template <class M> constexpr bool PL_FLAT = M::PHI_LDS > MAXORD && !M::PHI_GLOBAL && !M::W2;
-#endif
+// (cell_setup) so that an order that has never been written is finite.
+template <class M> constexpr bool PL_FLAT = M::PHI_LDS > MAXORD && !M::W2;
 #define PL_VEC(n) _Pragma("unroll") for (int k__ = 0; k__ < NTRIP; k__++) if (const int n = vrow<M>(k__, lane, wave_id()); vok<M>(k__, lane, wave_id()))
 // the same for statements that touch a vector in GLOBAL memory (NST entries: no padding there): always masked
 #define PL_VECG(n) _Pragma("unroll") for (int k__ = 0; k__ < NTRIP; k__++) if (const int n = vrow<M>(k__, lane, wave_id()); vokg<M>(k__, lane, wave_id()))
@@ -497,16 +490,10 @@ PL_DEV int ida_nls(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I, 
     if constexpr ((F & GF_EXPR) != 0) { if (xrun) { value = closure_input(S, *xrun, I.tn, S.yy, S.yp); *xvalue = value; } }       // closure input: run.func(t, Y, YP, p) inside every residual (scalar_residual.jl:169-170)
     if (callLSetup) {
       PL_TIC();
-#ifndef PL_EXP_NO_JAC
       cell_res_jac(S, R, S.yy, S.yp, S.delta, mode, value);
-#else
-      cell_residual(S, R, S.yy, S.yp, S.delta, mode, value);
-#endif
-#ifndef PL_EXP_NO_FACTOR
       bool genf = false;
       if constexpr ((F & GF_GENROW) != 0) { if (g && g->on()) { genf = true; gen_factor(S, R, tb, I.cj, mode, false, *g, I.tn, S.yy, S.yp, S.yp); } }   // (S.yp is dead until the next form_iterate; the row is evaluated before W overwrites it)
       if (!genf) cell_factor(S, R, tb, I.cj, mode, false);
-#endif
       cnt_add(cnt, C_RES); cnt_add(cnt, C_JAC); cnt_add(cnt, C_FACT);
       I.cjold = I.cj; I.cjratio = 1.0; I.ss = 20.0; jcur = 1; callLSetup = 0;
       PL_TOC(S, PH_JACFACT);
@@ -518,13 +505,11 @@ PL_DEV int ida_nls(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I, 
     }
     cnt_add(cnt, C_NEWTON); cnt_add(cnt, C_SOLVE);
     { PL_TIC();
-#ifndef PL_EXP_NO_SOLVE
     bool gens = false;
     if constexpr ((F & GF_GENROW) != 0) gens = g && g->on();
     if ((F & GF_REFINE) && nref > 0) cell_solve_refined(S, R, tb, S.delta, S.yp, I.cjold, mode, false, nref, gens ? g : nullptr);   // (S.yp is dead until the next form_iterate; cjold = cj of the factors)
     else if (gens) gen_solve(S, R, S.delta, false, *g);
     else cell_solve(S, R, S.delta, mode, false);           // x = J^-1 F ; the Newton correction is -x
-#endif
     PL_TOC(S, PH_SOLVE); }
     PL_TIC();
     const double sc = (I.cjratio != 1.0) ? -2.0 * pl_rcp(1.0 + I.cjratio) : -1.0;
@@ -705,7 +690,7 @@ PL_DEV bool ida_complete_step(CellLDS<M>& S, IdaScalars& I, double err_k, double
       if (ku >= 3) { PL_VEC(n) S.phi[3][n] = q[3][k__]; } else if (grow && ku == 2) { PL_VEC(n) S.phi[3][n] = EE(n); }
       if (ku >= 2) { PL_VEC(n) S.phi[2][n] = q[2][k__]; } else if (grow) { PL_VEC(n) S.phi[2][n] = EE(n); }           // (ku == 1 here)
       PL_VEC(n) { S.phi[1][n] = q[1][k__]; S.phi[0][n] = acc[k__]; }
-    } else if constexpr (PHI_REGS<M> && PL_BRANCHY_PHI) {      // (r03 form, kept for same-box A/B builds: tools/experiments/build_modes.py th_branchy)
+    } else if constexpr (PHI_REGS<M> && PL_BRANCHY_PHI) {      // (r03 form: what the thermal kernels are built with, -DPL_EXP_BRANCHY_PHI in petlion.jl_amd/buildflags.py, +2.5 % on C3)
       _Pragma("unroll") for (int j = MAXORD; j >= 0; j--) {
         if (j == ku + 1 && ku < I.maxord) { PL_VEC(n) PHI_WR(j, n, EE(n)); }
         else if (j == ku) { PL_VEC(n) { acc[k__] = PHI_RD(j, n) + EE(n); PHI_WR(j, n, acc[k__]); sp[k__] = dku * acc[k__]; } }
@@ -767,9 +752,7 @@ PL_DEV void ida_get_solution(CellLDS<M>& S, const IdaScalars& I, double t, doubl
   PL_GS_STEP(1, rp0, rp1, c1, d0) PL_GS_STEP(2, rp1, rp2, c2, d1) PL_GS_STEP(3, rp2, rp3, c3, d2) PL_GS_STEP(4, rp3, rp4, c4, d3) PL_GS_STEP(5, rp4, rp5, c5, d4)
 #undef PL_GS_STEP
   PL_VEC(n) {
-    // (history in global memory: orders beyond the one in use have never been written)
-    const double p1 = S.phi[1][n], p2 = (!M::PHI_GLOBAL || kord >= 2) ? PHI_RD(2, n) : 0.0, p3 = (!M::PHI_GLOBAL || kord >= 3) ? PHI_RD(3, n) : 0.0,
-                 p4 = (!M::PHI_GLOBAL || kord >= 4) ? PHI_RD(4, n) : 0.0, p5 = (!M::PHI_GLOBAL || kord >= 5) ? PHI_RD(5, n) : 0.0;
+    const double p1 = S.phi[1][n], p2 = PHI_RD(2, n), p3 = PHI_RD(3, n), p4 = PHI_RD(4, n), p5 = PHI_RD(5, n);
     double s = S.phi[0][n] + c1 * p1, sp = d0 * p1;
     if (kord >= 2) { s += c2 * p2; sp += d1 * p2; }
     if (kord >= 3) { s += c3 * p3; sp += d2 * p3; }
@@ -973,12 +956,11 @@ struct CellOut {
 template <int F, class M>
 PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double SOC0, const double* Yinit, double t_init, int n_runs, const plh_run* runs, const plh_opts& o,
                                      const CellOut& out, int* n_pts_out, plh_run_info* info, Counters& cnt, double* Yfin, double* YPfin,
-                                     double* Yprev, double* YPprev, int cell, double* genW = nullptr, SensArgs sens = SensArgs(), const double* th0 = nullptr, double* phig = nullptr,
+                                     double* Yprev, double* YPprev, int cell, double* genW = nullptr, SensArgs sens = SensArgs(), const double* th0 = nullptr,
                                      bool from_states = false) {
   PL_MODEL(M);
   const int lane = lane_id();
   IdaScalars I;
-  I.phg = phig;
   [[maybe_unused]] SensCell<M> SX;
   if constexpr ((F & GF_SENS) != 0) { SX.a = sens; SX.th0 = th0; SX.cell = cell; SX.P = tb->P; SX.max_pts = out.max_pts; SX.first = true; SX.n_it = 0; SX.n_fail = 0; SX.n_refresh = 0; }
   int nout = 0;
@@ -1166,11 +1148,7 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
       if (iter == o.maxiters) { flag = PLH_ERR_MAXITERS; break; }
       if (nout >= out.max_pts && out.max_pts > 0 && flag == PLH_FLAG_RUNNING) { flag = PLH_ERR_OUTPUT_FULL; break; }
       if (flag == PLH_FLAG_RUNNING) {
-#ifdef PL_EXP_STORE_PREV     /* (A/B build: r03's per-step copy of the whole previous point) */
-        PL_VECG(n) { Yprev[n] = S.yy[n]; YPprev[n] = S.yp[n]; }
-#else
         if (YPfin) { PL_VECG(n) YPprev[n] = S.yp[n]; }                // fire-and-forget: read back only when a bound fires (wave-uniform condition)
-#endif
         t_prev_saved = t + t0; I_prev_pt = S.yy[O_I];
         if constexpr ((F & GF_FUNC) != 0) if (is_fun && t - tprev < 1e-3 * o.reltol) {                    // check_reinitialization!, checks.jl:341-364
           const double t_new = t + o.reltol, v_new = run_input<F>(S, run, t_new, S.yy, S.yp);
@@ -1195,14 +1173,10 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
       const double fr = pv.frac;
       const double ti = fr * (t - tprev) + tprev;
       PL_XSYNC();
-#ifdef PL_EXP_STORE_PREV
-      PL_VECG(n) { S.yy[n] = fr * (S.yy[n] - Yprev[n]) + Yprev[n]; S.yp[n] = fr * (S.yp[n] - YPprev[n]) + YPprev[n]; }
-#else
       // (t > 1 excludes the point a run starts from: at least one step has been completed, phi[0] / phi[1] are those of the step that crossed the bound)
       if ((F & GF_FUNC) && steps_since_restart == 1) { PL_VECG(n) { const double yprev = Yprev[n]; S.yy[n] = fr * (S.yy[n] - yprev) + yprev; } }
       else { PL_VEC(n) { const double yprev = S.phi[0][n] - S.phi[1][n]; S.yy[n] = fr * (S.yy[n] - yprev) + yprev; } }
       if (YPfin) { PL_VECG(n) { const double ypp = YPprev[n]; S.yp[n] = fr * (S.yp[n] - ypp) + ypp; } }
-#endif
       PL_XSYNC();
       SOC = SOC + 0.5 * ((ti + t0) - (t + t0)) * (S.yy[O_I] + S.yy[O_I]) / 3600.0;
       t_end = ti + t0;

@@ -380,62 +380,35 @@ PL_DEV void thermal_cs_rows(CellLDS<M>& S, const Tables* __restrict__ tb, const 
   const int lane = lane_id();
   const CellConst& c = S.cc;
   auto& TP = S.th;
-  if constexpr (PL_THROWB) {
-    // r06, ROW layout (dfn_cell.h rowb_fmac): one particle per 16-lane DPP row, lane -> (particle = pass * 4 + lane / 16, row = lane % 16); the particle's vector costs one
-    // LDS load per lane and pass, the sums run over row_newbcast operands -- same terms, same order as the LDS form below
-    const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
-    double Mr_[NR], Wr_[WANT_JAC ? NR : 1];
-    for (int k = 0; k < NR; k++) { Mr_[k] = S.Mr[rc * NR + k]; if constexpr (WANT_JAC) Wr_[k] = S.Mr[S.OFF_WR + rc * NR + k]; }
-    [[maybe_unused]] double MrN[NR_EQ ? 1 : NR], WrN[(NR_EQ || !WANT_JAC) ? 1 : NR];
-    if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) { MrN[k] = S.Mr[S.mr_el(1) + rc * NR + k]; if constexpr (WANT_JAC) WrN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + rc * NR + k]; }
-    int pp[CSD_PASS]; double acc[CSD_PASS], wc[CSD_PASS], cv[CSD_PASS], jv[CSD_PASS], ypv[CSD_PASS], kp[CSD_PASS];
+  // r06, ROW layout (dfn_cell.h rowb_fmac): one particle per 16-lane DPP row, lane -> (particle = pass * 4 + lane / 16, row = lane % 16); the particle's vector costs one
+  // LDS load per lane and pass, the sums run over row_newbcast operands (terms in ascending k)
+  const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
+  double Mr_[NR], Wr_[WANT_JAC ? NR : 1];
+  for (int k = 0; k < NR; k++) { Mr_[k] = S.Mr[rc * NR + k]; if constexpr (WANT_JAC) Wr_[k] = S.Mr[S.OFF_WR + rc * NR + k]; }
+  [[maybe_unused]] double MrN[NR_EQ ? 1 : NR], WrN[(NR_EQ || !WANT_JAC) ? 1 : NR];
+  if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) { MrN[k] = S.Mr[S.mr_el(1) + rc * NR + k]; if constexpr (WANT_JAC) WrN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + rc * NR + k]; }
+  int pp[CSD_PASS]; double acc[CSD_PASS], wc[CSD_PASS], cv[CSD_PASS], jv[CSD_PASS], ypv[CSD_PASS], kp[CSD_PASS];
 #pragma unroll
-    for (int pass = 0; pass < CSD_PASS; pass++) {
-      const int p0 = pass * CSD_G + q; pp[pass] = p0 < NJ ? p0 : NJ - 1; acc[pass] = 0.0; wc[pass] = 0.0;
-      const int rk = rc < nr_of(pp[pass]) ? rc : nr_of(pp[pass]) - 1;
-      cv[pass] = Y[O_CS + cs_off(pp[pass]) + rk]; jv[pass] = Y[O_J + pp[pass]]; ypv[pass] = YP[O_CS + cs_off(pp[pass]) + rk]; kp[pass] = TP.kapP[pp[pass]];
-    }
-    csd_settle(cv);
-    static_for<0, NR>([&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-#pragma unroll
-      for (int pass = 0; pass < CSD_PASS; pass++) {
-        if constexpr (NR_EQ) { rowb_fmac<k>(acc[pass], cv[pass], Mr_[k]); if constexpr (WANT_JAC) rowb_fmac<k>(wc[pass], cv[pass], Wr_[k]); }
-        else { rowb_fmac<k>(acc[pass], cv[pass], pp[pass] < NP ? Mr_[k] : MrN[k]); if constexpr (WANT_JAC) rowb_fmac<k>(wc[pass], cv[pass], pp[pass] < NP ? Wr_[k] : WrN[k]); }
-      }
-    });
-#pragma unroll
-    for (int pass = 0; pass < CSD_PASS; pass++) {
-      const int p0 = pass * CSD_G + q, p = pp[pass];
-      double rhs = kp[pass] * acc[pass];
-      if (rr == nr_of(p) - 1) rhs += (p < NP ? c.bj_p : c.bj_n) * jv[pass];
-      if (p0 < NJ && rr < NR) { if (rr < nr_of(p)) Fo[O_CS + cs_off(p) + rr] = rhs - ypv[pass]; if (WANT_JAC) TP.AinvQ[p][rr] = wc[pass]; }
-    }
-    return;
+  for (int pass = 0; pass < CSD_PASS; pass++) {
+    const int p0 = pass * CSD_G + q; pp[pass] = p0 < NJ ? p0 : NJ - 1; acc[pass] = 0.0; wc[pass] = 0.0;
+    const int rk = rc < nr_of(pp[pass]) ? rc : nr_of(pp[pass]) - 1;
+    cv[pass] = Y[O_CS + cs_off(pp[pass]) + rk]; jv[pass] = Y[O_J + pp[pass]]; ypv[pass] = YP[O_CS + cs_off(pp[pass]) + rk]; kp[pass] = TP.kapP[pp[pass]];
   }
-  const int r = lane % NR, g = lane < CS_LANES ? lane / NR : CS_G - 1;
-  double Mrow[NR], Wrow[NR];
-  // (the radial operator from its LDS copy, as in the isothermal models: r03 fetched it from the table in global memory in every residual and every solve)
-  for (int k = 0; k < NR; k++) { Mrow[k] = S.Mr[r * NR + k]; if (WANT_JAC) Wrow[k] = S.Mr[S.OFF_WR + r * NR + k]; }
-  // (N_r_p != N_r_n: the anode's rows of M and W, zero-padded to the common stride like the cathode's -- a sum over k < NR is the sum over the particle's own rows, a lane
-  //  whose row does not exist in its particle computes 0 for W c and stores no residual)
-  [[maybe_unused]] double MrowN[NR_EQ ? 1 : NR], WrowN[NR_EQ ? 1 : NR];
-  if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) { MrowN[k] = S.Mr[S.mr_el(1) + r * NR + k]; if (WANT_JAC) WrowN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + r * NR + k]; }
+  csd_settle(cv);
+  static_for<0, NR>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
 #pragma unroll
-  for (int pass = 0; pass < CS_PASS; pass++) {
-    const int p0 = pass * CS_G + g, p = p0 < NJ ? p0 : NJ - 1;
-    double acc = 0.0, wc = 0.0;
-#pragma unroll
-    for (int k = 0; k < NR; k++) {
-      const double v = Y[O_CS + cs_off(p) + k];
-      if constexpr (NR_EQ) { acc += Mrow[k] * v; if (WANT_JAC) wc += Wrow[k] * v; }
-      else { acc += (p < NP ? Mrow[k] : MrowN[k]) * v; if (WANT_JAC) wc += (p < NP ? Wrow[k] : WrowN[k]) * v; }
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      if constexpr (NR_EQ) { rowb_fmac<k>(acc[pass], cv[pass], Mr_[k]); if constexpr (WANT_JAC) rowb_fmac<k>(wc[pass], cv[pass], Wr_[k]); }
+      else { rowb_fmac<k>(acc[pass], cv[pass], pp[pass] < NP ? Mr_[k] : MrN[k]); if constexpr (WANT_JAC) rowb_fmac<k>(wc[pass], cv[pass], pp[pass] < NP ? Wr_[k] : WrN[k]); }
     }
-    // (every load unconditional -- p is clamped --, only the stores guarded: a load under `if` is one exec-masked LDS round trip of its own)
-    const double jv = Y[O_J + p], ypv = YP[O_CS + cs_off(p) + r];
-    double rhs = TP.kapP[p] * acc;
-    if (r == nr_of(p) - 1) rhs += (p < NP ? c.bj_p : c.bj_n) * jv;
-    if (lane < CS_LANES && p0 < NJ) { if (r < nr_of(p)) Fo[O_CS + cs_off(p) + r] = rhs - ypv; if (WANT_JAC) TP.AinvQ[p][r] = wc; }
+  });
+#pragma unroll
+  for (int pass = 0; pass < CSD_PASS; pass++) {
+    const int p0 = pass * CSD_G + q, p = pp[pass];
+    double rhs = kp[pass] * acc[pass];
+    if (rr == nr_of(p) - 1) rhs += (p < NP ? c.bj_p : c.bj_n) * jv[pass];
+    if (p0 < NJ && rr < NR) { if (rr < nr_of(p)) Fo[O_CS + cs_off(p) + rr] = rhs - ypv[pass]; if (WANT_JAC) TP.AinvQ[p][rr] = wc[pass]; }
   }
 }
 
@@ -551,11 +524,7 @@ __device__ __forceinline__ void thermal_sweeps(const CellLDS<M>& S, bool alg_onl
   // far-behind share q . y(node N_p - 3) leaves r_{N_p - 1} once that y is final (after stage (N_p - 3) / 2); r_{N_p - 1} sits in TWO of the combined right-hand sides,
   // its own and the next node's (through -C_next r_{N_p - 1}), so the next lane gets + C_next[:, 3] x the same share.  Default-shaped grids only (both electrodes alike,
   // halves inside a DPP row); one right-hand side.
-#ifdef PL_NO_STRIDE2T
-  constexpr bool STRIDE2T = false;
-#else
   constexpr bool STRIDE2T = NRHS == 1 && FAR_T == FAR_B && FAR_T >= 1 && TW_FWD <= 15 && TW_MID <= 15;
-#endif
   if constexpr (STRIDE2T) {
     double P[16];
     {
@@ -704,105 +673,50 @@ __device__ __forceinline__ int wb_src_node(int k) { return k == 0 ? 2 : (k == 1 
 __device__ __forceinline__ int wb_row_node(int k) { return k == 0 ? 0 : (k == 1 ? NP - 1 : (k == 2 ? NP + NS : NE - 1)); }
 
 template <class M>
-PL_DEV_FACTOR void thermal_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb, double cj, int mode, bool alg_only) {
+PL_DEV void thermal_factor(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__ tb, double cj, int mode, bool alg_only) {
   PL_MODEL(M);
   const int lane = lane_id();
   const CellConst& c = S.cc;
   auto& TP = S.th;
-  const int r = lane % NR, g = lane < CS_LANES ? lane / NR : CS_G - 1;
   PL_TICD();
-  // 1. particle resolvents in spectral form: A_p^-1 = V diag(1 / (kappa_p lam_m - cj)) W.  Lane (g, r) owns mode r of its particles and forms the reciprocals of ITS modes
-  //    only (CS_PASS divisions per lane; r03 divided inside the sums: N_r CS_PASS of them).  They stay in registers for the solves (R.rcp) and are shared with the other
-  //    lanes of the particle through the c_s section of S.yy, which is dead between a residual evaluation and the next form_iterate (thermal_solve uses it the same way).
+  // 1. particle resolvents in spectral form: A_p^-1 = V diag(1 / (kappa_p lam_m - cj)) W.  A lane forms the reciprocals of ITS modes only (one division per lane and pass; r03
+  //    divided inside the sums) and keeps them in registers for the solves (R.rcp).
   if (!alg_only) {
     if (lane < NJ) TP.kapF[lane] = TP.kapP[lane];
-    if constexpr (PL_THROWB) {
-      // r06, ROW layout: lane (row q, rr) owns mode rr of particle pass * 4 + q.  The reciprocals and W c / d of a particle's modes sit in the lanes of its DPP row: the two
-      // sums over the modes take them through row_newbcast (rowb_fmac) -- no round trip through the c_s section of S.yy, no phase separator
-      const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
-      const double lam_r = NR_EQ ? PL_RADIAL_LAM[rc] : tb->LAMp(0)[rc];
-      [[maybe_unused]] const double lam_rN = NR_EQ ? 0.0 : tb->LAMp(1)[rc];
-      double VW[NR], VL[NR];                                  // V[r][m] W[m][last] and V[r][m] lam_m: the constant factors of the two sums
-      [[maybe_unused]] double VWN[NR_EQ ? 1 : NR], VLN[NR_EQ ? 1 : NR];
-      if constexpr (NR_EQ) { for (int m = 0; m < NR; m++) { const double v = S.Mr[S.OFF_VR + rc * NR + m]; VW[m] = v * PL_RADIAL_W[m * NR + NR - 1]; VL[m] = v * PL_RADIAL_LAM[m]; } }
-      else for (int m = 0; m < NR; m++) {
-        const double v = S.Mr[S.OFF_VR + rc * NR + m], vn = S.Mr[S.mr_el(1) + S.OFF_VR + rc * NR + m];
-        VW[m] = v * tb->Wp(0)[m * NR + NRP - 1]; VL[m] = v * tb->LAMp(0)[m]; VWN[m] = vn * tb->Wp(1)[m * NR + NRN - 1]; VLN[m] = vn * tb->LAMp(1)[m];
-      }
-      int pp[CSD_PASS]; double rcv[CSD_PASS], wq[CSD_PASS], ae[CSD_PASS], aq[CSD_PASS], dk[CSD_PASS];
-#pragma unroll
-      for (int pass = 0; pass < CSD_PASS; pass++) {
-        const int p0 = pass * CSD_G + q, pq = p0 < NJ ? p0 : NJ - 1; pp[pass] = pq;
-        R.rcp[pass] = pl_rcp(TP.kapP[pq] * ((NR_EQ || pq < NP) ? lam_r : lam_rN) - cj);
-        rcv[pass] = R.rcp[pass]; wq[pass] = TP.AinvQ[pq][rc] * R.rcp[pass];      // AinvQ still holds W c
-        dk[pass] = TP.dkapP[pq]; ae[pass] = 0.0; aq[pass] = 0.0;
-      }
-      csd_settle(rcv); csd_settle(wq);
-      static_for<0, NR>([&](auto mc) {
-        constexpr int m = decltype(mc)::value;
-#pragma unroll
-        for (int pass = 0; pass < CSD_PASS; pass++) {
-          if constexpr (NR_EQ) { rowb_fmac<m>(ae[pass], rcv[pass], VW[m]); rowb_fmac<m>(aq[pass], wq[pass], VL[m]); }
-          else { rowb_fmac<m>(ae[pass], rcv[pass], pp[pass] < NP ? VW[m] : VWN[m]); rowb_fmac<m>(aq[pass], wq[pass], pp[pass] < NP ? VL[m] : VLN[m]); }
-        }
-      });
-      PL_SYNC();                                             // every lane has read W c before it is overwritten
-#pragma unroll
-      for (int pass = 0; pass < CSD_PASS; pass++) {
-        const int p0 = pass * CSD_G + q;
-        if (p0 < NJ && rr < NR) { TP.AinvE[pp[pass]][rr] = ae[pass]; TP.AinvQ[pp[pass]][rr] = aq[pass] * dk[pass]; }
-      }
-    } else {
-    // (N_r_p != N_r_n: eigenvalues and W[:, last] of the particle's own electrode from the padded tables -- a padded mode has lam = 0, its reciprocal -1/cj meets V = 0 --; the
-    //  reciprocals are shared through the particle's own c_s entries of S.yy, S.yy[O_CS + cs_off(p) + mode])
-    const double lam_r = NR_EQ ? PL_RADIAL_LAM[r] : tb->LAMp(0)[r];
-    [[maybe_unused]] const double lam_rN = NR_EQ ? 0.0 : tb->LAMp(1)[r];
-    const int cs0 = PL_OPAQUE_IDX(g * NR + r);
-    double wc[CS_PASS];
-#pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g, p = p0 < NJ ? p0 : NJ - 1;
-      R.rcp[pass] = 1.0 / (TP.kapP[p] * ((NR_EQ || p < NP) ? lam_r : lam_rN) - cj);
-      wc[pass] = (&TP.AinvQ[0][0])[(p0 < NJ ? pass * CS_G * NR : (NJ - 1 - g) * NR) + cs0];      // AinvQ still holds W c  (clamped like p)
-    }
-#pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g;
-      if (lane < CS_LANES && p0 < NJ) {
-        if constexpr (NR_EQ) S.yy[O_CS + pass * CS_G * NR + cs0] = R.rcp[pass];
-        else { if (r < nr_of(p0)) S.yy[O_CS + cs_off(p0) + r] = R.rcp[pass]; }
-        (&TP.AinvQ[0][0])[pass * CS_G * NR + cs0] = wc[pass] * R.rcp[pass];
-      }
-    }
-    PL_SYNC();
+    // r06, ROW layout: lane (row q, rr) owns mode rr of particle pass * 4 + q.  The reciprocals and W c / d of a particle's modes sit in the lanes of its DPP row: the two
+    // sums over the modes take them through row_newbcast (rowb_fmac) -- no round trip through the c_s section of S.yy, no phase separator
+    const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
+    const double lam_r = NR_EQ ? PL_RADIAL_LAM[rc] : tb->LAMp(0)[rc];
+    [[maybe_unused]] const double lam_rN = NR_EQ ? 0.0 : tb->LAMp(1)[rc];
     double VW[NR], VL[NR];                                  // V[r][m] W[m][last] and V[r][m] lam_m: the constant factors of the two sums
     [[maybe_unused]] double VWN[NR_EQ ? 1 : NR], VLN[NR_EQ ? 1 : NR];
-    if constexpr (NR_EQ) { for (int m = 0; m < NR; m++) { const double v = S.Mr[S.OFF_VR + r * NR + m]; VW[m] = v * PL_RADIAL_W[m * NR + NR - 1]; VL[m] = v * PL_RADIAL_LAM[m]; } }
+    if constexpr (NR_EQ) { for (int m = 0; m < NR; m++) { const double v = S.Mr[S.OFF_VR + rc * NR + m]; VW[m] = v * PL_RADIAL_W[m * NR + NR - 1]; VL[m] = v * PL_RADIAL_LAM[m]; } }
     else for (int m = 0; m < NR; m++) {
-      const double v = S.Mr[S.OFF_VR + r * NR + m], vn = S.Mr[S.mr_el(1) + S.OFF_VR + r * NR + m];
+      const double v = S.Mr[S.OFF_VR + rc * NR + m], vn = S.Mr[S.mr_el(1) + S.OFF_VR + rc * NR + m];
       VW[m] = v * tb->Wp(0)[m * NR + NRP - 1]; VL[m] = v * tb->LAMp(0)[m]; VWN[m] = vn * tb->Wp(1)[m * NR + NRN - 1]; VLN[m] = vn * tb->LAMp(1)[m];
     }
-    double ae[CS_PASS], aq[CS_PASS];
-    const int pg0 = PL_OPAQUE_IDX(g * NR);
+    int pp[CSD_PASS]; double rcv[CSD_PASS], wq[CSD_PASS], ae[CSD_PASS], aq[CSD_PASS], dk[CSD_PASS];
 #pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g;
-      const int base = p0 < NJ ? pass * CS_G * NR + pg0 : (NJ - 1) * NR;
-      ae[pass] = 0.0; aq[pass] = 0.0;
-      if constexpr (NR_EQ) {
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      const int p0 = pass * CSD_G + q, pq = p0 < NJ ? p0 : NJ - 1; pp[pass] = pq;
+      R.rcp[pass] = pl_rcp(TP.kapP[pq] * ((NR_EQ || pq < NP) ? lam_r : lam_rN) - cj);
+      rcv[pass] = R.rcp[pass]; wq[pass] = TP.AinvQ[pq][rc] * R.rcp[pass];      // AinvQ still holds W c
+      dk[pass] = TP.dkapP[pq]; ae[pass] = 0.0; aq[pass] = 0.0;
+    }
+    csd_settle(rcv); csd_settle(wq);
+    static_for<0, NR>([&](auto mc) {
+      constexpr int m = decltype(mc)::value;
 #pragma unroll
-        for (int m = 0; m < NR; m++) { ae[pass] += VW[m] * S.yy[O_CS + base + m]; aq[pass] += VL[m] * (&TP.AinvQ[0][0])[base + m]; }
-      } else {
-        const int pc = p0 < NJ ? p0 : NJ - 1;
-        for (int m = 0; m < NR; m++) { ae[pass] += (pc < NP ? VW[m] : VWN[m]) * S.yy[O_CS + cs_off(pc) + m]; aq[pass] += (pc < NP ? VL[m] : VLN[m]) * (&TP.AinvQ[0][0])[base + m]; }
+      for (int pass = 0; pass < CSD_PASS; pass++) {
+        if constexpr (NR_EQ) { rowb_fmac<m>(ae[pass], rcv[pass], VW[m]); rowb_fmac<m>(aq[pass], wq[pass], VL[m]); }
+        else { rowb_fmac<m>(ae[pass], rcv[pass], pp[pass] < NP ? VW[m] : VWN[m]); rowb_fmac<m>(aq[pass], wq[pass], pp[pass] < NP ? VL[m] : VLN[m]); }
       }
-    }
-    PL_SYNC();                                             // every lane has read the shared reciprocals and W c / d before they are overwritten
+    });
+    PL_SYNC();                                             // every lane has read W c before it is overwritten
 #pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g, p = p0 < NJ ? p0 : NJ - 1;
-      if (lane < CS_LANES && p0 < NJ) { TP.AinvE[p][r] = ae[pass]; TP.AinvQ[p][r] = aq[pass] * TP.dkapP[p]; }
-    }
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      const int p0 = pass * CSD_G + q;
+      if (p0 < NJ && rr < NR) { TP.AinvE[pp[pass]][rr] = ae[pass]; TP.AinvQ[pp[pass]][rr] = aq[pass] * dk[pass]; }
     }
     // 2. collector chains: (aL, aD - cj, aU) x = rhs by the Thomas algorithm, lane 32 + k = collector node k (systolic DPP chains as in thermal_solve: one LDS load per
     //    operand and lane).  Two fixed right-hand sides: the coupling to T of the neighbouring cell node (Al: last row, through aU; Cu: first row, through aL) and the column of I
@@ -1042,7 +956,6 @@ PL_DEV void thermal_solve(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__
   const int lane = lane_id();
   const CellConst& c = S.cc;
   auto& TP = S.th;
-  const int r = lane % NR, g = lane < CS_LANES ? lane / NR : CS_G - 1;
   PL_TICE(2);
   // a. particle partial solutions w = A_p^-1 b_cs  (two mat-vecs through the spectral form, the diagonal from R.rcp); collector forward/backward substitution
   double zbk = 0.0;                                        // lane 32 + k: chain solution of collector node k (T^-1 b_T restricted to the chain)
@@ -1067,111 +980,58 @@ PL_DEV void thermal_solve(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__
       for (int st = 1; st < NC; st++) { const double xn = shift_down1(x); x = (f - up * xn) * cpk; }
       zbk = x;
     };
-    if constexpr (PL_THROWB) {
-      double yvr[CSD_PASS];                                 // W b / d per pass, handed from the first mat-vec to the second in registers
-        // r06, ROW layout: y = diag(1 / (kappa lam - cj)) W b with b through row_newbcast; the second mat-vec (below, behind the collector chains) takes y from the lanes of
-        // the row as well -- r05 wrote y to the c_s section of S.yy and read it back behind a phase separator
-        const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
-        double Wr_[NR];
-        for (int k = 0; k < NR; k++) Wr_[k] = S.Mr[S.OFF_WR + rc * NR + k];
-        [[maybe_unused]] double WrN[NR_EQ ? 1 : NR];
-        if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) WrN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + rc * NR + k];
-        int pp[CSD_PASS]; double bc[CSD_PASS];
-  #pragma unroll
-        for (int pass = 0; pass < CSD_PASS; pass++) {
-          const int p0 = pass * CSD_G + q; pp[pass] = p0 < NJ ? p0 : NJ - 1; yvr[pass] = 0.0;
-          const int rk = rc < nr_of(pp[pass]) ? rc : nr_of(pp[pass]) - 1;
-          bc[pass] = b[O_CS + cs_off(pp[pass]) + rk];
-        }
-        csd_settle(bc);
-        static_for<0, NR>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-  #pragma unroll
-          for (int pass = 0; pass < CSD_PASS; pass++) {
-            if constexpr (NR_EQ) rowb_fmac<k>(yvr[pass], bc[pass], Wr_[k]);
-            else rowb_fmac<k>(yvr[pass], bc[pass], pp[pass] < NP ? Wr_[k] : WrN[k]);
-          }
-        });
-  #pragma unroll
-        for (int pass = 0; pass < CSD_PASS; pass++) yvr[pass] *= R.rcp[pass];
-      collectors();
-      // second mat-vec: w = V y with y from the lanes of the row (registers: no LDS round trip, no phase separator)
-      {
-        const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
-        double Vr_[NR];
-        for (int m = 0; m < NR; m++) Vr_[m] = S.Mr[S.OFF_VR + rc * NR + m];
-        [[maybe_unused]] double VrN[NR_EQ ? 1 : NR];
-        if constexpr (!NR_EQ) for (int m = 0; m < NR; m++) VrN[m] = S.Mr[S.mr_el(1) + S.OFF_VR + rc * NR + m];
-        double w[CSD_PASS];
+    double yvr[CSD_PASS];                                 // W b / d per pass, handed from the first mat-vec to the second in registers
+    // r06, ROW layout: y = diag(1 / (kappa lam - cj)) W b with b through row_newbcast; the second mat-vec (below, behind the collector chains) takes y from the lanes of
+    // the row as well -- r05 wrote y to the c_s section of S.yy and read it back behind a phase separator
+    const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
+    double Wr_[NR];
+    for (int k = 0; k < NR; k++) Wr_[k] = S.Mr[S.OFF_WR + rc * NR + k];
+    [[maybe_unused]] double WrN[NR_EQ ? 1 : NR];
+    if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) WrN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + rc * NR + k];
+    int pp[CSD_PASS]; double bc[CSD_PASS];
 #pragma unroll
-        for (int pass = 0; pass < CSD_PASS; pass++) w[pass] = 0.0;
-        csd_settle(yvr);
-        static_for<0, NR>([&](auto mc) {
-          constexpr int m = decltype(mc)::value;
-#pragma unroll
-          for (int pass = 0; pass < CSD_PASS; pass++) {
-            const int p0 = pass * CSD_G + q, pc = p0 < NJ ? p0 : NJ - 1;
-            if constexpr (NR_EQ) rowb_fmac<m>(w[pass], yvr[pass], Vr_[m]);
-            else rowb_fmac<m>(w[pass], yvr[pass], pc < NP ? Vr_[m] : VrN[m]);
-          }
-        });
-#pragma unroll
-        for (int pass = 0; pass < CSD_PASS; pass++) {
-          const int p0 = pass * CSD_G + q;
-          if (p0 < NJ && rr == nr_of(p0 < NJ ? p0 : NJ - 1) - 1) S.w9[p0] = w[pass];
-          R.wreg[pass] = w[pass];
-        }
-      }
-    } else {
-    double Wrow[NR], Vrow[NR];
-    for (int k = 0; k < NR; k++) { Wrow[k] = S.Mr[S.OFF_WR + r * NR + k]; Vrow[k] = S.Mr[S.OFF_VR + r * NR + k]; }
-    // (one address register per array for the lane's particle group; pass and column go into the offset fields.  The last pass may reach beyond the last particle: its
-    //  lanes read the last particle instead -- same values as a clamped index, selected per lane on the ADDRESS)
-    constexpr int LASTP = (CS_PASS - 1) * CS_G;             // first particle of the last pass
-    const bool over = LASTP + g >= NJ;
-    constexpr bool A16 = NR % 2 == 0 && O_CS % 2 == 0;      // particle rows start on 16-byte boundaries (b is one of the 16-byte aligned vectors of CellLDS)
-    const lds_cptr bg = PL_LDS_BASE_A(A16, (const double*)b + O_CS + g * NR), bl = PL_LDS_BASE_A(A16, (const double*)b + O_CS + (over ? NJ - 1 : LASTP + g) * NR);
-    // (N_r_p != N_r_n: per-electrode rows of W and V, zero-padded; the particles sit at cs_off(p) in b and in S.yy, plain indexing instead of the affine address tricks)
-    [[maybe_unused]] double WrowN[NR_EQ ? 1 : NR], VrowN[NR_EQ ? 1 : NR];
-    if constexpr (!NR_EQ) for (int k = 0; k < NR; k++) { WrowN[k] = S.Mr[S.mr_el(1) + S.OFF_WR + r * NR + k]; VrowN[k] = S.Mr[S.mr_el(1) + S.OFF_VR + r * NR + k]; }
-    double yv[CS_PASS];
-#pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      double y = 0.0;
-      if constexpr (NR_EQ) {
-        const lds_cptr bb = pass == CS_PASS - 1 ? bl : bg + pass * CS_G * NR;
-#pragma unroll
-        for (int k = 0; k < NR; k++) y += Wrow[k] * bb[k];
-      } else {
-        const int p0 = pass * CS_G + g, pc = p0 < NJ ? p0 : NJ - 1;
-        for (int k = 0; k < NR; k++) y += (pc < NP ? Wrow[k] : WrowN[k]) * b[O_CS + cs_off(pc) + k];
-      }
-      yv[pass] = y * R.rcp[pass];
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      const int p0 = pass * CSD_G + q; pp[pass] = p0 < NJ ? p0 : NJ - 1; yvr[pass] = 0.0;
+      const int rk = rc < nr_of(pp[pass]) ? rc : nr_of(pp[pass]) - 1;
+      bc[pass] = b[O_CS + cs_off(pp[pass]) + rk];
     }
-    const lds_ptr yg = PL_LDS_BASE(S.yy + O_CS + g * NR + r);
+    csd_settle(bc);
+    static_for<0, NR>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
 #pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      if constexpr (NR_EQ) { if (lane < CS_LANES && pass * CS_G + g < NJ) yg[pass * CS_G * NR] = yv[pass]; }   // S.yy is dead between a residual and the next form_iterate
-      else { const int p0 = pass * CS_G + g; if (lane < CS_LANES && p0 < NJ && r < nr_of(p0)) S.yy[O_CS + cs_off(p0) + r] = yv[pass]; }
-    }
+      for (int pass = 0; pass < CSD_PASS; pass++) {
+        if constexpr (NR_EQ) rowb_fmac<k>(yvr[pass], bc[pass], Wr_[k]);
+        else rowb_fmac<k>(yvr[pass], bc[pass], pp[pass] < NP ? Wr_[k] : WrN[k]);
+      }
+    });
+#pragma unroll
+    for (int pass = 0; pass < CSD_PASS; pass++) yvr[pass] *= R.rcp[pass];
     collectors();
-    PL_SYNC();
-    const lds_cptr yr = PL_LDS_BASE_A(A16, (const double*)S.yy + O_CS + g * NR), yl = PL_LDS_BASE_A(A16, (const double*)S.yy + O_CS + (over ? NJ - 1 : LASTP + g) * NR);
+    // second mat-vec: w = V y with y from the lanes of the row (registers: no LDS round trip, no phase separator)
+    {
+      double Vr_[NR];
+      for (int m = 0; m < NR; m++) Vr_[m] = S.Mr[S.OFF_VR + rc * NR + m];
+      [[maybe_unused]] double VrN[NR_EQ ? 1 : NR];
+      if constexpr (!NR_EQ) for (int m = 0; m < NR; m++) VrN[m] = S.Mr[S.mr_el(1) + S.OFF_VR + rc * NR + m];
+      double w[CSD_PASS];
 #pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g;
-      double w = 0.0;
-      if constexpr (NR_EQ) {
-        const lds_cptr yb = pass == CS_PASS - 1 ? yl : yr + pass * CS_G * NR;
+      for (int pass = 0; pass < CSD_PASS; pass++) w[pass] = 0.0;
+      csd_settle(yvr);
+      static_for<0, NR>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
 #pragma unroll
-        for (int m = 0; m < NR; m++) w += Vrow[m] * yb[m];
-      } else {
-        const int pc = p0 < NJ ? p0 : NJ - 1;
-        for (int m = 0; m < NR; m++) w += (pc < NP ? Vrow[m] : VrowN[m]) * S.yy[O_CS + cs_off(pc) + m];
+        for (int pass = 0; pass < CSD_PASS; pass++) {
+          const int p0 = pass * CSD_G + q, pc = p0 < NJ ? p0 : NJ - 1;
+          if constexpr (NR_EQ) rowb_fmac<m>(w[pass], yvr[pass], Vr_[m]);
+          else rowb_fmac<m>(w[pass], yvr[pass], pc < NP ? Vr_[m] : VrN[m]);
+        }
+      });
+#pragma unroll
+      for (int pass = 0; pass < CSD_PASS; pass++) {
+        const int p0 = pass * CSD_G + q;
+        if (p0 < NJ && rr == nr_of(p0 < NJ ? p0 : NJ - 1) - 1) S.w9[p0] = w[pass];
+        R.wreg[pass] = w[pass];
       }
-      if (lane < CS_LANES && p0 < NJ && r == nr_of(p0) - 1) S.w9[p0] = w;
-      R.wreg[pass] = w;
-    }
     }
   }
   PL_SYNC();
@@ -1261,38 +1121,20 @@ PL_DEV void thermal_solve(CellLDS<M>& S, LaneRegs& R, const Tables* __restrict__
   PL_SYNC();
   PL_TOCE(S, 2, 3);
   // f. particles: dc = w - A^-1 e_last bj dj - A^-1 q dT
-  if constexpr (PL_THROWB) {
-    if (!alg_only) {       // ROW layout
-      const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
-      double ae[CSD_PASS], aq[CSD_PASS], dj[CSD_PASS], dT[CSD_PASS];
+  if (!alg_only) {       // ROW layout
+    const int q = lane >> 4, rr = lane & 15, rc = rr < NR ? rr : NR - 1;
+    double ae[CSD_PASS], aq[CSD_PASS], dj[CSD_PASS], dT[CSD_PASS];
 #pragma unroll
-      for (int pass = 0; pass < CSD_PASS; pass++) {
-        const int p0 = pass * CSD_G + q, p = p0 < NJ ? p0 : NJ - 1, ndp = p < NP ? p : p + NS;
-        ae[pass] = TP.AinvE[p][rc]; aq[pass] = TP.AinvQ[p][rc]; dj[pass] = b[O_J + p]; dT[pass] = b[O_T + NA + ndp];
-      }
-#pragma unroll
-      for (int pass = 0; pass < CSD_PASS; pass++) {
-        const int p0 = pass * CSD_G + q, p = p0 < NJ ? p0 : NJ - 1;
-        const double bj = p < NP ? c.bj_p : c.bj_n;
-        const double v = R.wreg[pass] - ae[pass] * bj * dj[pass] - aq[pass] * dT[pass];
-        if (p0 < NJ && rr < nr_of(p)) b[O_CS + cs_off(p) + rr] = v;
-      }
-    }
-  } else
-  if (!alg_only) {
-    // (unconditional clamped loads first, guarded stores last -- see iso_solve)
-    double ae[CS_PASS], aq[CS_PASS], dj[CS_PASS], dT[CS_PASS];
-#pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p0 = pass * CS_G + g, p = p0 < NJ ? p0 : NJ - 1, nd = p < NP ? p : p + NS;
-      ae[pass] = TP.AinvE[p][r]; aq[pass] = TP.AinvQ[p][r]; dj[pass] = b[O_J + p]; dT[pass] = b[O_T + NA + nd];
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      const int p0 = pass * CSD_G + q, p = p0 < NJ ? p0 : NJ - 1, ndp = p < NP ? p : p + NS;
+      ae[pass] = TP.AinvE[p][rc]; aq[pass] = TP.AinvQ[p][rc]; dj[pass] = b[O_J + p]; dT[pass] = b[O_T + NA + ndp];
     }
 #pragma unroll
-    for (int pass = 0; pass < CS_PASS; pass++) {
-      const int p = pass * CS_G + g;
+    for (int pass = 0; pass < CSD_PASS; pass++) {
+      const int p0 = pass * CSD_G + q, p = p0 < NJ ? p0 : NJ - 1;
       const double bj = p < NP ? c.bj_p : c.bj_n;
       const double v = R.wreg[pass] - ae[pass] * bj * dj[pass] - aq[pass] * dT[pass];
-      if (lane < CS_LANES && p < NJ && r < nr_of(p)) b[O_CS + cs_off(p) + r] = v;
+      if (p0 < NJ && rr < nr_of(p)) b[O_CS + cs_off(p) + rr] = v;
     }
   }
   PL_SYNC();

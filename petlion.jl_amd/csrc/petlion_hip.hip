@@ -181,7 +181,6 @@ template <class T> struct Uploaded {
 struct StreamCtx {
   hipStream_t st = nullptr;
   DevBuf scratch;                                           // [n_cells][2][N]: previous accepted point of every cell (back-interpolation)
-  DevBuf phig;                                              // [n_cells][4][NPAD]: BDF history orders 2 .. 5 of the variants that keep them in global memory (VariantOps::phig_doubles)
   DevBuf genW;                                              // [n_cells][N]: border vector of the general control row (closure inputs with derivative programs)
   Uploaded<plh_run> runs;                                   // the protocol (remembered when it is plain: a repeated launch with the same protocol uploads nothing and does not synchronise)
   Uploaded<double> tdiscon, tstops;                         // opts.tdiscon / opts.tstops, sorted
@@ -579,7 +578,7 @@ void plh_model_destroy(plh_model_t m) {
   for (void* p : m->d_tables) hipFree(p);
   if (m->d_tb) hipFree(m->d_tb);
   for (StreamCtx* c : m->streams) {
-    for (DevBuf* b : {&c->scratch, &c->genW, &c->phig, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf, &c->resample, &c->resample_tq.buf}) b->free();
+    for (DevBuf* b : {&c->scratch, &c->genW, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf, &c->resample, &c->resample_tq.buf}) b->free();
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->ret_ev) hipEventDestroy(e);
@@ -1168,9 +1167,8 @@ static int integrate_impl(plh_model_t m, int n, const double* theta, const doubl
   IntegrateArgs a;
   a.tb = m->d_tb; a.n_cells = n; a.n_runs = n_runs; a.opts = *opts;
   HIPCHK(cx.scratch.reserve(cx.st, (size_t)n * 2 * m->N * sizeof(double)));
-  if (m->ops->phig_doubles > 0) HIPCHK(cx.phig.reserve(cx.st, (size_t)n * m->ops->phig_doubles * sizeof(double)));
   if (need_genW) HIPCHK(cx.genW.reserve(cx.st, (size_t)n * m->N * sizeof(double)));
-  a.scratch = (double*)cx.scratch.d; a.genW = need_genW ? (double*)cx.genW.d : nullptr; a.phig = m->ops->phig_doubles > 0 ? (double*)cx.phig.d : nullptr;
+  a.scratch = (double*)cx.scratch.d; a.genW = need_genW ? (double*)cx.genW.d : nullptr;
   // inputs: the caller's arrays, then what is always host memory -- time lists, selection map, protocol -- as device copies kept per stream
   a.theta = s.in(theta, (size_t)n * m->P); a.SOC0 = s.in(SOC0, n);
   a.Y_init = s.in(Y_init, (size_t)n * m->N); a.t_init = s.in(t_init, n);

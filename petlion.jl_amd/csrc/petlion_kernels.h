@@ -18,15 +18,12 @@ namespace pl {
 // (tools/kernel_resources.py -> petlion.jl_amd/libpetlion_hip.so.resources.json) and committed for the validated binary in profiles/validated_build.json
 // ("kernel_resources"); tests/test_build_records.py fails when a plain benchmark kernel of the isothermal / SEI models uses scratch.  No figures are typed in here: r05's
 // said "0 B/lane" for the thermal kernel while the shipped object had 28.  (rocprofv3's `accum_vgpr_count` reads 0 on this unified-file part and is not the figure to read.)
-#if !defined(PL_WAVE_EMU) && !defined(PL_NO_WAVES_ATTR) && defined(PL_WAVES_PER_EU)
-// -DPL_WAVES_PER_EU=n: experiment builds (tools/experiments/occupancy.py)
-#define PL_ONE_WAVE_PER_SIMD __attribute__((amdgpu_waves_per_eu(PL_WAVES_PER_EU, PL_WAVES_PER_EU)))
-#elif !defined(PL_WAVE_EMU) && !defined(PL_NO_WAVES_ATTR)      /* (PL_NO_WAVES_ATTR: experiment builds of tools/experiments/build_modes.py) */
+#ifndef PL_WAVE_EMU
 // One cell per SIMD (one wave with 512 registers; M::W2: its two waves with 256 each) for every model whose cell fills a quarter of the CU's LDS -- the 301-state models.  A cell
-// of <= 26 624 B leaves room for at least six on a CU: those kernels are compiled for TWO cells per SIMD (256 registers per lane).  Measured r05 (tools/experiments/occupancy.py):
+// of <= 26 624 B leaves room for at least six on a CU: those kernels are compiled for TWO cells per SIMD (256 registers per lane).  Measured r05:
 // quadratic particles (20.7 kB, 7 cells per CU) +42 %, polynomial +39 %, the (2, 2, 2, 10) grid (12.2 kB, 8 per CU) +63 %; three per SIMD +25 % only (168 registers).  The
-// 301-state models reach 26.2 kB only with the history in global memory (-DPL_OCC2, ModelT::PHI_GLOBAL) and lose 5 % there: they stay at one.
-#define PL_CELLS_PER_SIMD(M) ((sizeof(CellLDS<M>) <= (M::PHI_GLOBAL ? 32768 : 26624) && !M::W2) ? 2 : 1)      /* (the PL_OCC2 experiment layouts: five cells per CU count too) */
+// 301-state models got that small only with the BDF history in global memory and lost 5 % there (measured, then removed: DESIGN.md 2): they stay at one.
+#define PL_CELLS_PER_SIMD(M) ((sizeof(CellLDS<M>) <= 26624 && !M::W2) ? 2 : 1)
 #define PL_ONE_WAVE_PER_SIMD __attribute__((amdgpu_waves_per_eu(M::NWAVES * PL_CELLS_PER_SIMD(M), M::NWAVES * PL_CELLS_PER_SIMD(M))))
 #else
 #define PL_ONE_WAVE_PER_SIMD
@@ -157,7 +154,7 @@ template <class M, int F> __global__ __launch_bounds__(64 * M::NWAVES) PL_ONE_WA
                 a.out.run_info + (size_t)cell * a.n_runs, cnt,
                 a.out.Y_final ? a.out.Y_final + (size_t)cell * NST : nullptr, a.out.YP_final ? a.out.YP_final + (size_t)cell * NST : nullptr,
                 a.scratch + (size_t)cell * 2 * NST, a.scratch + (size_t)cell * 2 * NST + NST, cell, a.genW ? a.genW + (size_t)cell * NST : nullptr, a.sens, a.theta + (size_t)cell * a.tb->P,
-                (M::PHI_GLOBAL && a.phig) ? a.phig + (size_t)cell * (MAXORD + 1 - M::PHI_LDS) * M::NPADG : nullptr, a.Y_init && !a.t_init);
+                a.Y_init && !a.t_init);
   PL_TOC_TOTAL(S);
   PL_SYNC();
   if (threadIdx.x == 0 && a.out.counters) {
@@ -357,7 +354,7 @@ template <class M> struct OpsOf {
     static_assert(!GRID_DEFAULT || sizeof(CellLDS<M>) <= 40960, "built-in variant: LDS per cell above 40 960 B, only three cells per CU would be resident");
 #endif
     static const VariantOps ops = {id, M::CHEM, M::SEI ? 1 : 0, M::THERMAL ? 1 : 0, M::PREC, M::SD, M::TF, M::RXN, M::W2 ? 1 : 0, M::NST, M::NDIFF, {NP, NS, NN, NRP, NA, NZ, NRN},
-                                   {PL_RADIAL_M, PL_RADIAL_M_N}, {PL_RADIAL_LAM, PL_RADIAL_LAM_N}, {PL_RADIAL_V, PL_RADIAL_V_N}, {PL_RADIAL_W, PL_RADIAL_W_N}, {PL_RADIAL_BJ_FACTOR, PL_RADIAL_BJ_FACTOR_N}, sizeof(CellLDS<M>), (int)(sizeof(CellLDS<M>) / sizeof(double)) + M::NWAVES * WAVE * 2 * LR_PASS, M::PHI_GLOBAL ? (MAXORD + 1 - M::PHI_LDS) * M::NPADG : 0, &classify<M>, &sections_of<M>,
+                                   {PL_RADIAL_M, PL_RADIAL_M_N}, {PL_RADIAL_LAM, PL_RADIAL_LAM_N}, {PL_RADIAL_V, PL_RADIAL_V_N}, {PL_RADIAL_W, PL_RADIAL_W_N}, {PL_RADIAL_BJ_FACTOR, PL_RADIAL_BJ_FACTOR_N}, sizeof(CellLDS<M>), (int)(sizeof(CellLDS<M>) / sizeof(double)) + M::NWAVES * WAVE * 2 * LR_PASS, &classify<M>, &sections_of<M>,
                                    &initial_guess, &residual, &jacobian, &linear_solve, &init_consistent, &integrate};
     return &ops;
   }

@@ -34,7 +34,6 @@ struct IntegrateArgs {
   plh_outputs out; double* scratch;   // scratch: [n_cells][2][NST]
   double* genW;                       // [n_cells][NST] or nullptr: border vector of the general control row (closures with derivative programs)
   pl::SensArgs sens;                  // forward parameter sensitivities (dfn_sens.h); n_sens = 0: none
-  double* phig;                       // [n_cells][4][NPAD] or nullptr: BDF history orders 2 .. 5 of the variants that keep them in global memory (ModelT::PHI_GLOBAL)
   const int* sel_map; int sel_tot;    // out.Y_sel: packed entry k of a saved row is state sel_map[k] ([sel_tot] DEVICE ints built from out.sel, which is host memory and never read by a kernel)
 };
 
@@ -47,7 +46,6 @@ struct VariantOps {
   const double *rad_M[2], *rad_LAM[2], *rad_V[2], *rad_W[2]; double rad_BJ[2];       // radial operator tables of N_r_p / N_r_n (radial_tables.h), N_r x N_r packed
   size_t lds_bytes;                                                                  // sizeof(CellLDS<M>): LDS per cell (= per workgroup)
   int fsave_doubles;                                                                 // doubles per cell a sensitivity step needs to park the integrator's factorisation (dfn_sens.h, sens_factor_copy)
-  int phig_doubles;                                                                  // doubles of global-memory BDF history per cell (0: the history is LDS / register resident)
   unsigned (*classify)(const pl::Tables& tb, int mode, int r, int c);              // decode word of the structural Jacobian entry (r, c), 0 if structurally zero
   int (*sections)(SectionInfo* out);
   void (*initial_guess)(hipStream_t st, const pl::Tables* tb, int n, const double* theta, const double* SOC, double* Y);
@@ -70,5 +68,5 @@ PL_VARIANT_LIST(PL_DECLARE_OPS)
 extern "C" const VariantOps* plh_grid_variant_ops(int id);     // nullptr: variant not built into this grid library
 extern "C" void plh_grid_dims(int* grid7);
 // what a grid library was compiled against: bump PLH_HOST_ABI whenever VariantOps / IntegrateArgs / Tables change, so that a stale cached library is refused, not misread
-constexpr int PLH_HOST_ABI = 10;
+constexpr int PLH_HOST_ABI = 11;
 extern "C" void plh_grid_abi(int* abi, int* sizeof_ops, int* sizeof_args, int* sizeof_tables);

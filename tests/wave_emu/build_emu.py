@@ -12,7 +12,7 @@ OUT = os.path.join(HERE, "libpetlion_emu.so")
 
 def build(force=False, variant=None, extra=(), tag=""):
     """variant=<id>: a developer's quick build holding that one model variant (libpetlion_emu_v<id>.so, ~20 s instead of ~2 min); the tests use the full library"""
-    out = OUT if variant is None else OUT[:-3] + "_v%d%s.so" % (variant, tag)            # (extra / tag: experiment builds, e.g. -DPL_OCC2)
+    out = OUT if variant is None else OUT[:-3] + "_v%d%s.so" % (variant, tag)            # (extra / tag: builds with a test switch, e.g. -DPL_TEST_SENS_FORCE_REFRESH)
     deps = [SRC] + [os.path.join(os.path.dirname(SRC), f) for f in os.listdir(os.path.dirname(SRC)) if f.endswith((".h", ".hip"))]
     deps.append(os.path.join(HERE, "hip", "hip_runtime.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):

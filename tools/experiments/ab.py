@@ -11,32 +11,23 @@ LATE = ["-DPL_DEV=__device__ inline", "-mllvm", "-amdgpu-function-calls=false"]
 EARLY = ["-DPL_DEV=__device__ __forceinline__"]
 NOLSO = ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
 NOVEC = ["-mllvm", "-amdgpu-load-store-vectorizer=0"]
-# (r04 note: -DPL_EXP_UNI, -DPL_EXP_SWEEP_REGS, -DPL_EXP_SEI_PRED and -DPL_EXP_ALL_PRED selected code paths that have since been adopted (sweep blocks in registers, SEI predictor
-#  in registers) or removed (uni(), thermal predictor in registers): the entries that name them are the record of what was measured -- gpurun_out/r04k..r04m, DESIGN.md 5a -- and
-#  now build the tree as it is)
+# (entries whose switch has left the source -- adopted or measured slower and removed, DESIGN.md 5a -- are deleted with it: git history keeps them)
 NOLICM = ["-mllvm", "-disable-machine-licm"]          # r04: MachineLICM hoists (among others) the copies of the exp / log polynomial coefficients out of the step loop
-UNI = ["-DPL_EXP_UNI"]                                # r04: wave-uniform doubles of the step loop handed to scalar registers (uni(), dfn_cell.h)
 BUILDS = {
     "th_prod": ([4], EARLY + NOLSO + NOVEC, "c3", "c3_thermal"),
-    "th_nolicm": ([4], EARLY + NOLSO + NOVEC + NOLICM, "c3", "c3_thermal"), "th_uni": ([4], EARLY + NOLSO + NOVEC + UNI, "c3", "c3_thermal"),
-    "th_uni_nolicm": ([4], EARLY + NOLSO + NOVEC + UNI + NOLICM, "c3", "c3_thermal"),
-    "iso_nolicm": ([0], LATE + NOLICM, "c2 c4", "c2_1024 or evaluators"), "iso_uni": ([0], LATE + UNI, "c2 c4", "c2_1024 or evaluators"),
-    "iso_uni_nolicm": ([0], LATE + UNI + NOLICM, "c2 c4", "c2_1024 or evaluators"),
-    "sei_pred_nolicm": ([3], LATE + UNI + NOLICM + ["-DPL_EXP_SEI_PRED"], "c5", "c5_nmc_sei"),
-    "th_late_nolicm": ([4], LATE + NOLSO + NOVEC + UNI + NOLICM, "c3", "c3_thermal"), "iso_early_nolicm": ([0], EARLY + UNI + NOLICM, "c2 c4", "c2_1024 or evaluators"),
-    "th_merge_nolicm": ([4], EARLY + UNI + NOLICM, "c3", "c3_thermal"),          # (DS merging back on, now that 16-byte register tuples are no longer scarce)
+    "th_nolicm": ([4], EARLY + NOLSO + NOVEC + NOLICM, "c3", "c3_thermal"),
+    "iso_nolicm": ([0], LATE + NOLICM, "c2 c4", "c2_1024 or evaluators"),
     # (the sweep's blocks in registers: adopted in the source after th_sweepregs, +2.5 %) combinations on top of it:
     "th_new": ([4], EARLY + NOLSO + NOVEC + NOLICM, "c3", "c3_thermal"), "th_new_merge": ([4], EARLY + NOLICM, "c3", "c3_thermal"),
     "th_new_late_merge": ([4], LATE + NOLICM, "c3", "c3_thermal"), "th_new_late": ([4], LATE + NOLSO + NOVEC + NOLICM, "c3", "c3_thermal"),
-    "th_new_pred": ([4], EARLY + NOLSO + NOVEC + NOLICM + ["-DPL_EXP_ALL_PRED"], "c3", "c3_thermal"),          # predictor of the step in registers for the thermal model too
     "th_branchy_nolicm": ([4], EARLY + NOLSO + NOVEC + NOLICM + ["-DPL_EXP_BRANCHY_PHI"], "c3", "c3_thermal"), "th_branchy_merge": ([4], EARLY + NOLICM + ["-DPL_EXP_BRANCHY_PHI"], "c3", "c3_thermal"),
     "th_fence": ([4], EARLY + NOLSO + NOVEC + NOLICM + ["-DPL_PHASE_FENCES"], "c3", "c3_thermal"), "iso_fence": ([0], LATE + NOLICM + ["-DPL_PHASE_FENCES"], "c2 c4", "c2_1024 or evaluators"),
     "sei_fence": ([3], LATE + NOLICM + ["-DPL_PHASE_FENCES"], "c5", "c5_nmc_sei"), "iso_new": ([0], LATE + NOLICM, "c2 c4", "c2_1024 or evaluators"), "sei_new": ([3], LATE + NOLICM, "c5", "c5_nmc_sei"),
     "th_fb": ([4], EARLY + NOLSO + NOVEC + NOLICM + ["-DPL_PHASE_FENCES", "-DPL_EXP_BRANCHY_PHI"], "c3", "c3_thermal"),          # = the production thermal build since the end of r04
     "lgm_fb": ([14], EARLY + NOLSO + NOVEC + NOLICM + ["-DPL_PHASE_FENCES", "-DPL_EXP_BRANCHY_PHI"], "", ""),          # variant 14 with the flags of variants 4 / 7 (selftest_delta.py)
     "lgm_nolicm": ([14], EARLY + NOLSO + NOVEC + NOLICM, "", ""), "lgm_licm": ([14], EARLY + NOLSO + NOVEC, "", ""),          # (tools/dbg/selftest_delta.py)
-    "sei_pred2": ([3], LATE + NOLICM + ["-DPL_EXP_SEI_PRED"], "c5", "c5_nmc_sei"), "iso_early2": ([0], EARLY + NOLICM, "c2 c4", "c2_1024 or evaluators"),
-    "sei_nolicm": ([3], LATE + NOLICM, "c5", "c5_nmc_sei"), "sei_uni_nolicm": ([3], LATE + UNI + NOLICM, "c5", "c5_nmc_sei"),
+    "iso_early2": ([0], EARLY + NOLICM, "c2 c4", "c2_1024 or evaluators"),
+    "sei_nolicm": ([3], LATE + NOLICM, "c5", "c5_nmc_sei"),
     "th_base": ([4], EARLY, "c3", "c3_thermal"),
     "th_branchy": ([4], EARLY + ["-DPL_EXP_BRANCHY_PHI"], "c3", "c3_thermal"),          # r03's branching update of the register-resident BDF history
     "iso_base": ([0], LATE, "c2 c4", "c2_1024 or evaluators"),
@@ -46,18 +37,15 @@ BUILDS = {
     "th_nolso": ([4], EARLY + NOLSO, "c3", "c3_thermal"), "iso_nolso": ([0], LATE + NOLSO, "c2 c4", "c2_1024 or evaluators"), "sei_nolso": ([3], LATE + NOLSO, "c5", "c5_nmc_sei"),
     "th_novec": ([4], EARLY + NOLSO + NOVEC, "c3", "c3_thermal"), "iso_novec": ([0], LATE + NOLSO + NOVEC, "c2 c4", "c2_1024 or evaluators"),
     # round-3 final source (built from a git worktree of that commit into the same _exp/ directory: `git worktree add /tmp/r03 <commit>`; build only lists them for `run`)
-    "sei_pred": ([3], LATE + ["-DPL_EXP_SEI_PRED"], "c5", "c5_nmc_sei"),          # r04: predictor of the step in registers for the SEI models (PRED_REGS)
     "th_r03": ([4], None, "c3", "c3_thermal"), "iso_r03": ([0], None, "c2 c4", "c2_1024 or evaluators"), "sei_r03": ([3], None, "c5", "c5_nmc_sei"),
 }
-# r06: the instruction / latency diet of the isothermal kernels (variant 0, production flag table): everything on, and one switch off at a time
+# r06: the instruction / latency diet of the isothermal kernels (variant 0, production flag table): the tree as it is against the library-math fall-back
 BUILDS.update({
-    "r06_all": ([0], [], "c2 c4", "c2_1024 or evaluators"), "r06_noflat": ([0], ["-DPL_NO_FLAT"], "c2 c4", "c2_1024 or evaluators"),
-    "r06_novpad": ([0], ["-DPL_NO_VPAD"], "c2 c4", "c2_1024 or evaluators"), "r06_ieeediv": ([0], ["-DPL_IEEE_DIV"], "c2 c4", "c2_1024 or evaluators"),
-    "r06_none": ([0], ["-DPL_NO_FLAT", "-DPL_NO_VPAD", "-DPL_IEEE_DIV"], "c2 c4", "c2_1024 or evaluators"),
-    "r06c_all": ([0], [], "c2 c4", "c2_1024 or evaluators"), "r06c_lane1": ([0], ["-DPL_LANE_OPAQUE=1"], "c2 c4", "c2_1024 or evaluators"),
-    "r06d_all": ([0], [], "c2 c4", "c2_1024 or evaluators"), "r06d_nocsdpp": ([0], ["-DPL_NO_CSDPP"], "c2 c4", "c2_1024 or evaluators"),
-    "th_r06f": ([4], [], "c3", "c3_thermal"), "th_r06f_nothrowb": ([4], ["-DPL_NO_THROWB"], "c3", "c3_thermal"),
-    "th_r06g": ([4], [], "c3", "c3_thermal"), "th_r06g_nostride2": ([4], ["-DPL_NO_STRIDE2T"], "c3", "c3_thermal"),          # one level of recursive doubling in the 4x4 sweeps of a solve
+    "r06_all": ([0], [], "c2 c4", "c2_1024 or evaluators"), "r06_ieeediv": ([0], ["-DPL_IEEE_DIV"], "c2 c4", "c2_1024 or evaluators"),
+    "r06c_all": ([0], [], "c2 c4", "c2_1024 or evaluators"),
+    "r06d_all": ([0], [], "c2 c4", "c2_1024 or evaluators"),
+    "th_r06f": ([4], [], "c3", "c3_thermal"),
+    "th_r06g": ([4], [], "c3", "c3_thermal"),
     "r05": ([0], None, "c2 c4", "c2_1024 or evaluators"),          # the r05 library as committed (copied to _exp/libplh_r05.so)
     "r06v": ([0], None, "c2 c4", "c2_1024 or evaluators"),
     "r06g_both": ([0], None, "c2 c4", "c2_1024 or evaluators"), "r06g_sei": ([3], None, "c5", "c5_nmc_sei"), "r06g_sei_ocml": ([3], None, "c5", "c5_nmc_sei"),          # + the sweep blocks formed together
@@ -65,8 +53,6 @@ BUILDS.update({
     "th_r06h_exp": ([4], None, "c3", "c3_thermal"), "th_r06h_ocml": ([4], None, "c3", "c3_thermal"),         # the validated r06 library (copied to _exp/libplh_r06v.so)
     "r06e_base": ([0], [], "c2 c4", "c2_1024 or evaluators"), "r06e_sw": ([0], ["-DPL_SWCACHE"], "c2 c4", "c2_1024 or evaluators"),          # blocks of the doubled sweeps kept in registers from the factorisation
 })
-for k in list(BUILDS):          # every build also exists with the previous-point copy kept (r03) or dropped
-    pass
 
 
 def lib_of(name):
