@@ -301,6 +301,42 @@ function resample(m::Model, ens, field::Array{Float64}, tq::Vector{Float64}; int
     (x, status)
 end
 
+"""
+    lsq(m, ens, tq, V_data; weights = nothing, interp_bc = :interpolate, resid = false)
+
+Weighted least-squares misfit of every cell's voltage curve against measured data (`plh_lsq`): with `S_V` the spline of `resample(m, ens, ens.V, tq)` and `S_k` the same
+spline through row k of `ens.dV_dθ` (an ensemble of `simulate_ensemble_sens`; without that field the misfit alone), `r = w (S_V(tq) - V_data)`, `J[:, k] = w S_k(tq)`.
+`V_data` and `weights` are vectors of length n_q (shared by all cells) or n_q × n matrices; a point with weight 0 is left out.  At most 8 sensitivity rows.
+Returns `(cost, grad, JtJ, resid, status)`: `cost` n, `grad` n_sens × n, `JtJ` n_sens × n_sens × n (`nothing` without sensitivities), `resid` n_q × n or `nothing`.
+"""
+function lsq(m::Model, ens, tq::Vector{Float64}, V_data::Array{Float64}; weights = nothing, interp_bc = :interpolate, resid = false)
+    interp_bc ∈ (:interpolate, :extrapolate) || error("Invalid interp_bc method.")
+    max_pts, n = size(ens.t)
+    n_runs, n_q = size(ens.run_info, 1), length(tq)
+    dV = hasproperty(ens, :dV_dθ) ? ens.dV_dθ : nothing
+    ns = dV === nothing ? 0 : size(dV, 2)
+    ns <= 8 || error("lsq takes at most 8 sensitivity rows per call")
+    per_cell = ndims(V_data) == 2 || (weights !== nothing && ndims(weights) == 2)
+    full(a) = ndims(a) == 2 ? a : repeat(a, 1, n)
+    y = per_cell ? full(V_data) : V_data
+    w = weights === nothing ? nothing : (per_cell ? full(weights) : weights)
+    size(y) == (per_cell ? (n_q, n) : (n_q,)) && (w === nothing || size(w) == size(y)) || error("V_data and weights must be n_q or n_q × n_cells")
+    cost = zeros(n); status = zeros(Cint, n)
+    grad = ns > 0 ? zeros(ns, n) : nothing
+    JtJ = ns > 0 ? zeros(ns, ns, n) : nothing
+    res = resid ? zeros(n_q, n) : nothing
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve dV y w grad JtJ res begin
+        check(ccall((:plh_lsq, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{RunInfo}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
+                    m.h, n, n_runs, max_pts, ens.t, ens.n_pts, ens.run_info, ens.V, ns, p(dV), n_q, tq, p(y), p(w), per_cell ? 1 : 0, interp_bc == :extrapolate ? 1 : 0,
+                    cost, p(grad), p(JtJ), p(res), status, PLH_HOST, C_NULL),
+              "plh_lsq")
+    end
+    (cost = cost, grad = grad, JtJ = JtJ, resid = res, status = status)
+end
+
 # ---- seam 1: the five generated functions of p.funcs (src/structures.jl:315-334) as single-cell evaluators ----
 function residual!(res::Vector{Float64}, m::Model, Y, YP, θ; mode = :I, value = 0.0)
     check(ccall((:plh_residual, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cvoid}),

@@ -385,6 +385,34 @@ int plh_resample(plh_model_t m, int n_cells, int n_runs, int max_pts, const doub
                  int width, const double* src, int n_q, const double* tq, int extrapolate,
                  double* dst /* [n_cells][n_q][width] */, int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
 
+/* ---- the weighted least-squares misfit of every cell's voltage curve against measured data, with its gradient and Gauss-Newton matrix when the ensemble was integrated by
+ * plh_integrate_sens: what a fit needs per cell and iteration (1 + n_sens + n_sens^2 numbers) instead of the curves and their Jacobian.
+ * S_V and S_k are exactly plh_resample's functions of V[cell] and of row k of dV_dtheta[cell]: the same run-assignment rule, the same not-a-knot cubic with the same
+ * n = 3 / 2 / 1 fall-backs, the same clamping (extrapolate = 0) or continuation (1).  With measurement times tq_q, data y_q and weights w_q:
+ *   r_q    = w_q (S_V(tq_q) - y_q)
+ *   J_qk   = w_q S_k(tq_q)
+ *   cost   = 1/2 sum_q r_q^2
+ *   grad_k = sum_q J_qk r_q
+ *   JtJ_kl = sum_q J_qk J_ql
+ *   resid[q] = r_q
+ * J is the derivative of the resampled curve AT FIXED KNOTS: the dependence of the saved times on theta is ignored, as it is for every post-interpolated output.
+ * Points left out: a point with w_q == 0 is not evaluated -- it contributes nothing, its resid is 0, and a NaN tq_q or y_q there is harmless.  A point with w_q != 0 and a
+ * NaN tq_q or y_q makes cost NaN, and the sums it enters.
+ * Cells that cannot be resampled (plh_resample's rule, status[cell] = 1): cost, grad, JtJ and resid rows are NaN, none of the cell's points is read, other cells do not
+ * notice.  NaN in a cell's dV_dtheta (the documented NaN cases of the sensitivities) reaches grad and JtJ of that cell only; cost and resid stay finite.
+ * n_sens == 0 is the misfit-only call (ensembles run without sensitivities): dV_dtheta, grad and JtJ are then NULL -- and only then.
+ * tq[n_q]: HOST memory for every ptr_kind (staged like plh_resample's tq).  y and w follow ptr_kind; w may be NULL (= 1); per_cell = 0: y[n_q], w[n_q] shared by all cells,
+ * 1: y[n_cells][n_q], w[n_cells][n_q].  PLH_HOST blocks, PLH_DEVICE is asynchronous on `stream`.  The slopes of the 1 + n_sens columns live in plh_resample's per-stream
+ * workspace, bounded the same way (PLH_RESAMPLE_WS_BYTES); the result does not depend on the chunking and is bit-identical between the two pointer kinds.
+ * PLH_E_ARG, nothing clamped: n_cells, n_runs, max_pts or n_q < 1; n_sens outside 0 .. PLH_LSQ_MAX_SENS; per_cell or extrapolate not 0 / 1; a NULL among t, n_pts, run_info,
+ * V, tq, y, cost; dV_dtheta / grad / JtJ NULL-ness that does not match n_sens. */
+#define PLH_LSQ_MAX_SENS 8
+int plh_lsq(plh_model_t m, int n_cells, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info,
+            const double* V /* [n_cells][max_pts] */, int n_sens, const double* dV_dtheta /* [n_cells][n_sens][max_pts] */,
+            int n_q, const double* tq, const double* y, const double* w, int per_cell, int extrapolate,
+            double* cost /* [n_cells] */, double* grad /* [n_cells][n_sens] */, double* JtJ /* [n_cells][n_sens][n_sens], full symmetric */,
+            double* resid /* [n_cells][n_q] or NULL */, int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

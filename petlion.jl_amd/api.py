@@ -841,6 +841,7 @@ def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, 
             bufs["dY_dtheta"], bufs["dV_dtheta"], bufs["sens_stat"] = np.empty((n, ns, N)), np.empty((n, ns, mp)), np.zeros((n, 3), np.int32)
         if Y_init is not None:
             raise ValueError("sensitivities are integrated for new solutions only")
+        bufs["sens_keys"] = list(sens)
         cap.check(lib, lib.plh_integrate_sens(h, n, cap.ptr(theta), cap.ptr(SOC0), len(runs), arr, C.byref(os_), C.byref(out), ns, cols.ctypes.data,
                                               cap.ptr(bufs["dY_dtheta"]), cap.ptr(bufs["dV_dtheta"]), cap.ptr(bufs["sens_stat"]), kind, stream), "plh_integrate_sens")
     else:
@@ -880,6 +881,15 @@ class ResampledEnsemble:
         raise KeyError("%r was not resampled: the ensemble needs sections=(%r,) or outputs='all', and ens(t, fields=...) must include it" % (name, name))
 
 
+class EnsembleFit:
+    """ens.lsq(t, V_data): the least-squares misfit of every cell's voltage curve against data (EnsembleSolution.lsq).  cost [cell]; grad [cell, k] and JtJ [cell, k, k] with
+    respect to the ensemble's `sens` keys (.keys), None for an ensemble run without them; resid [cell, n_q] when asked for, else None; status [cell]."""
+
+    def __init__(self, keys):
+        self.keys = list(keys)
+        self.cost = self.grad = self.JtJ = self.resid = self.status = None
+
+
 class EnsembleSolution:
     """Per-cell results of an ensemble run (arrays indexed [cell, point]); sol[i] gives a single-cell Solution."""
 
@@ -901,6 +911,7 @@ class EnsembleSolution:
         self.call_ms = bufs.get("call_ms")      # wall time of the plh_integrate call itself (host pointers: includes the copies back)
         # forward parameter sensitivities (simulate_ensemble(..., sens=[keys])): [cell, k, state] at the end of the protocol, [cell, k, point] for the voltage
         self.dY_dtheta, self.dV_dtheta, self.sens_stat = bufs.get("dY_dtheta"), bufs.get("dV_dtheta"), bufs.get("sens_stat")
+        self.keys = list(bufs.get("sens_keys") or [])      # the `sens` names, in the order of the k axis
 
     # With device=True the launch is asynchronous: the per-cell summaries stay in HBM until they are looked at (the first access synchronises),
     # so a host loop can enqueue launches back to back.
@@ -982,6 +993,65 @@ class EnsembleSolution:
             ext = torch.cuda.ExternalStream(int(stream), device=dev)      # (allocated on torch's current stream, written on the launch stream: as in _integrate)
             for v in made:
                 v.record_stream(ext)
+        return out
+
+    def lsq(self, t, V_data, weights=None, interp_bc="interpolate", resid=False):
+        """The weighted least-squares misfit of every cell's voltage curve against measured data on the device (plh_lsq; csrc/plh_lsq.h), and -- for an ensemble run with
+        sens=[keys] -- its gradient and Gauss-Newton matrix with respect to those keys: with S_V = ens(t).V and S_k the same spline through row k of dV_dtheta,
+        r = w (S_V(t) - V_data), J[:, k] = w S_k(t), cost = r.r / 2, grad = J'r, JtJ = J'J per cell (J at fixed knots: the saved times' dependence on the parameters is
+        ignored, as for every post-interpolated output).  t [n_q]; V_data and weights [n_q] (shared by all cells) or [n_cells, n_q]; weights = None: ones.  A point with
+        weight 0 is left out (a NaN time or datum there is harmless).  interp_bc as ens(t).  A device=True ensemble takes and returns torch tensors in HBM, queued on the
+        launch stream; a host ensemble numpy arrays.  Returns an EnsembleFit: .cost [n], .grad [n, k], .JtJ [n, k, k] (None without sens), .resid [n, n_q] (resid=True) or
+        None, .status [n] (1: the cell failed or was cut at max_points -- its rows are NaN), .keys."""
+        if interp_bc not in ("interpolate", "extrapolate"):
+            raise ValueError("Invalid interp_bc method.")
+        tq = np.ascontiguousarray(np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=np.float64))
+        if tq.ndim != 1 or tq.size < 1:
+            raise ValueError("t must be a 1-D array of measurement times")
+        n, mp = self.t.shape
+        ns = 0 if self.dV_dtheta is None else int(self.dV_dtheta.shape[1])
+        if ns > cap.LSQ_MAX_SENS:
+            raise ValueError("ens.lsq takes at most %d sens keys per call (this ensemble has %d)" % (cap.LSQ_MAX_SENS, ns))
+        device = not isinstance(self.t, np.ndarray)
+        if device:
+            import torch
+            dev = self.t.device
+            conv = lambda a: (a if hasattr(a, "device") else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
+            mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
+            kind, stream, rinfo = cap.PLH_DEVICE, self._stream, self._run_info_raw
+        else:
+            conv = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+            mk = lambda *shape, dt=np.float64: np.empty(shape, dt)
+            kind, stream, rinfo = cap.PLH_HOST, None, np.ascontiguousarray(self.run_info)
+        ext = None
+        if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            # data made or converted on torch's current stream are read on the launch stream: that stream waits for them, and the allocator learns of their use there
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)
+        y = conv(V_data)
+        w = None if weights is None else conv(weights)
+        for what, a in (("V_data", y), ("weights", w)):
+            if a is not None and tuple(a.shape) not in ((tq.size,), (n, tq.size)):
+                raise ValueError("%s must be [n_q] or [n_cells, n_q] = [%d] or [%d, %d], not %s" % (what, tq.size, n, tq.size, list(a.shape)))
+        per_cell = 1 if y.ndim == 2 or (w is not None and w.ndim == 2) else 0
+        if per_cell:                                            # (one form for both)
+            y = y if y.ndim == 2 else conv(y.expand(n, tq.size) if device else np.broadcast_to(y, (n, tq.size)))
+            w = w if w is None or w.ndim == 2 else conv(w.expand(n, tq.size) if device else np.broadcast_to(w, (n, tq.size)))
+        if ext is not None:
+            ext.wait_stream(torch.cuda.current_stream(dev))
+        out = EnsembleFit(self.keys)
+        out.cost, out.status = mk(n), mk(n, dt=torch.int32 if device else np.int32)
+        if ns:
+            out.grad, out.JtJ = mk(n, ns), mk(n, ns, ns)
+        if resid:
+            out.resid = mk(n, tq.size)
+        lib, h = self.p._lib, self.p._h
+        cap.check(lib, lib.plh_lsq(h, n, len(self.run_names), mp, cap.ptr(self.t), cap.ptr(self.n_pts), cap.ptr(rinfo), cap.ptr(self.V), ns, cap.ptr(self.dV_dtheta) if ns else None,
+                                   tq.size, tq.ctypes.data, cap.ptr(y), cap.ptr(w), per_cell, 1 if interp_bc == "extrapolate" else 0,
+                                   cap.ptr(out.cost), cap.ptr(out.grad), cap.ptr(out.JtJ), cap.ptr(out.resid), cap.ptr(out.status), kind, stream), "plh_lsq")
+        if ext is not None:
+            for v in (y, w, out.cost, out.grad, out.JtJ, out.resid, out.status):
+                if v is not None:
+                    v.record_stream(ext)
         return out
 
     def __getitem__(self, i):

@@ -35,6 +35,7 @@
 #endif
 
 #include "plh_resample.h"
+#include "plh_lsq.h"
 
 using namespace pl;
 
@@ -1224,6 +1225,24 @@ int plh_integrate_sens(plh_model_t m, int n, const double* theta, const double* 
 // ---- plh_resample: one per-point field of an ensemble on a time grid shared by all cells (kernels and algorithm: plh_resample.h) ----
 // The slopes need a workspace of max_pts x width doubles per cell -- a second copy of the field.  It is kept per stream and bounded: the cells are processed in chunks
 // (successive launches on the stream) of at most PLH_RESAMPLE_WS_BYTES of workspace (environment, read at every call; default 256 MiB; never less than one cell).
+// (shared with plh_lsq, whose columns are V and the rows of dV_dtheta: cells per chunk -- `blocks_per_cell` of the widest launch bounds the grid -- and the chunk's workspace)
+static int resample_work(StreamCtx& cx, int n, int n_runs, int max_pts, int n_q, int width, size_t blocks_per_cell, size_t* chunk_out, plrs::Work* w) {
+  size_t budget = (size_t)256 << 20;
+  if (const char* e = getenv("PLH_RESAMPLE_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  const size_t per = plrs::work_bytes_per_cell(n_runs, max_pts, n_q, width);
+  size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
+  chunk = std::max<size_t>(1, std::min(chunk, std::min<size_t>(0x7fffffffu / blocks_per_cell, (size_t)0x7fffffffu * plrs::TILE / (size_t)n_q)));      // (grid sizes of the launches)
+  HIPCHK(cx.resample.reserve(cx.st, chunk * per));
+  char* b = (char*)cx.resample.d;
+  w->fac = (double*)b; b += chunk * max_pts * 2 * sizeof(double);
+  w->loc_t = (double*)b; b += chunk * n_q * sizeof(double);
+  w->slope = (double*)b; b += chunk * max_pts * width * sizeof(double);
+  w->ok = (int*)b; b += chunk * sizeof(int);
+  w->run0 = (int*)b; b += chunk * n_runs * sizeof(int);
+  w->loc_i = (int*)b;
+  *chunk_out = chunk;
+  return 0;
+}
 int plh_resample(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, int width, const double* src,
                  int n_q, const double* tq, int extrapolate, double* dst, int* status, int kind, void* stream) {
   CHECK_MODEL(m); CHECK_KIND(kind);
@@ -1240,20 +1259,8 @@ int plh_resample(plh_model_t m, int n, int n_runs, int max_pts, const double* t,
   CHECK_STAGE(s);
   const double* d_tq = nullptr;
   if (int rc = cx.resample_tq.get(cx.st, std::vector<double>(tq, tq + n_q), &d_tq)) return rc;
-  size_t budget = (size_t)256 << 20;
-  if (const char* e = getenv("PLH_RESAMPLE_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-  const size_t per = plrs::work_bytes_per_cell(n_runs, max_pts, n_q, width), n_tiles = ((size_t)width + plrs::TILE - 1) / plrs::TILE;
-  size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
-  chunk = std::max<size_t>(1, std::min(chunk, std::min<size_t>(0x7fffffffu / n_tiles, (size_t)0x7fffffffu * plrs::TILE / (size_t)n_q)));      // (grid sizes of the launches)
-  HIPCHK(cx.resample.reserve(cx.st, chunk * per));
-  plrs::Work w;
-  { char* b = (char*)cx.resample.d;
-    w.fac = (double*)b; b += chunk * max_pts * 2 * sizeof(double);
-    w.loc_t = (double*)b; b += chunk * n_q * sizeof(double);
-    w.slope = (double*)b; b += chunk * max_pts * width * sizeof(double);
-    w.ok = (int*)b; b += chunk * sizeof(int);
-    w.run0 = (int*)b; b += chunk * n_runs * sizeof(int);
-    w.loc_i = (int*)b; }
+  size_t chunk = 0; plrs::Work w;
+  if (int rc = resample_work(cx, n, n_runs, max_pts, n_q, width, ((size_t)width + plrs::TILE - 1) / plrs::TILE, &chunk, &w)) return rc;
   for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
     plrs::Args a;
     a.cell0 = (int)c0; a.n_chunk = (int)std::min(chunk, (size_t)n - c0);
@@ -1263,6 +1270,44 @@ int plh_resample(plh_model_t m, int n, int n_runs, int max_pts, const double* t,
   }
   FINISH(s);
   s.back(dst, d_dst, n_dst); s.back(status, d_status, (size_t)n); CHECK_STAGE(s);
+  return 0;
+}
+
+// ---- plh_lsq: misfit of the voltage curves against data, gradient and Gauss-Newton matrix per cell (kernels: plh_lsq.h; the slopes of V and of the rows of dV_dtheta share
+// plh_resample's workspace and its chunking) ----
+int plh_lsq(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, const double* V, int n_sens,
+            const double* dV_dtheta, int n_q, const double* tq, const double* y, const double* w, int per_cell, int extrapolate,
+            double* cost, double* grad, double* JtJ, double* resid, int* status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1 || n_runs < 1 || max_pts < 1 || n_q < 1) return fail(PLH_E_ARG, "plh_lsq: n_cells, n_runs, max_pts and n_q must be >= 1");
+  if (n_sens < 0 || n_sens > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_lsq: n_sens must be 0 .. PLH_LSQ_MAX_SENS (8)");
+  if ((per_cell != 0 && per_cell != 1) || (extrapolate != 0 && extrapolate != 1)) return fail(PLH_E_ARG, "plh_lsq: per_cell and extrapolate must be 0 or 1");
+  if (!t || !n_pts || !run_info || !V || !tq || !y || !cost) return fail(PLH_E_ARG, "plh_lsq: null array (only w, resid and status may be NULL)");
+  if ((n_sens > 0) != (dV_dtheta != nullptr) || (n_sens > 0) != (grad != nullptr) || (n_sens > 0) != (JtJ != nullptr))
+    return fail(PLH_E_ARG, "plh_lsq: dV_dtheta, grad and JtJ are given with n_sens > 0 and NULL with n_sens == 0");
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  StreamCtx& cx = *s.cx;
+  const size_t pts = (size_t)n * max_pts, n_data = per_cell ? (size_t)n * n_q : (size_t)n_q, ns = (size_t)n_sens;
+  pllsq::Args A;
+  plrs::Args& a = A.rs;
+  a.t = s.in(t, pts); a.n_pts = s.in(n_pts, (size_t)n); a.run_info = s.in(run_info, (size_t)n * n_runs);
+  A.V = s.in(V, pts); A.dV = s.in(dV_dtheta, pts * ns); A.y = s.in(y, n_data); A.w = s.in(w, n_data);
+  A.cost = s.buf(cost, (size_t)n, false); A.grad = s.buf(grad, n * ns, false); A.JtJ = s.buf(JtJ, n * ns * ns, false); A.resid = s.buf(resid, (size_t)n * n_q, false);
+  a.status = s.buf(status, (size_t)n, false);
+  CHECK_STAGE(s);
+  if (int rc = cx.resample_tq.get(cx.st, std::vector<double>(tq, tq + n_q), &a.tq)) return rc;
+  size_t chunk = 0;
+  if (int rc = resample_work(cx, n, n_runs, max_pts, n_q, 1 + n_sens, 1, &chunk, &a.w)) return rc;
+  a.n_runs = n_runs; a.max_pts = max_pts; a.width = 1 + n_sens; a.n_q = n_q; a.extrapolate = extrapolate; a.src = nullptr; a.dst = nullptr;
+  A.n_sens = n_sens; A.per_cell = per_cell;
+  for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+    a.cell0 = (int)c0; a.n_chunk = (int)std::min(chunk, (size_t)n - c0);
+    pllsq::launch_chunk(s.st, A);
+  }
+  FINISH(s);
+  s.back(cost, A.cost, (size_t)n); s.back(grad, A.grad, n * ns); s.back(JtJ, A.JtJ, n * ns * ns); s.back(resid, A.resid, (size_t)n * n_q); s.back(status, a.status, (size_t)n);
+  CHECK_STAGE(s);
   return 0;
 }
 
