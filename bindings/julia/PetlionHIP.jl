@@ -245,15 +245,34 @@ function simulate_ensemble(m::Model, p, Θ::Matrix{Float64}, protocol; SOC = p.o
      flag = [info[end, i].flag for i in 1:n], t_end = [info[end, i].t_end for i in 1:n])
 end
 
+# plh_sens_outputs / plh_lsq_channel (include/petlion_hip.h): pointers only
+struct SensOutputs
+    dY_dtheta::Ptr{Cdouble}
+    dV_dtheta::Ptr{Cdouble}
+    dI_dtheta::Ptr{Cdouble}
+    dT_avg_dtheta::Ptr{Cdouble}
+    sens_stat::Ptr{Cint}
+end
+struct LsqChannel
+    curve::Ptr{Cdouble}
+    dcurve::Ptr{Cdouble}
+    y::Ptr{Cdouble}
+    w::Ptr{Cdouble}
+    resid::Ptr{Cdouble}
+end
+
 """
-    simulate_ensemble_sens(m, p, Θ, protocol, keys; SOC, max_pts)
+    simulate_ensemble_sens(m, p, Θ, protocol, keys; SOC, max_pts, outputs = (:V,))
 
 `simulate_ensemble` with forward sensitivities (`plh_integrate_sens`): `keys` = the θ Symbols to differentiate (entries of `m.θ_keys`).  Adds
 `dY_dθ[:, k, i]` = ∂Y/∂θ[keys[k]] of cell i at the end of the protocol and `dV_dθ[:, k, i]` = ∂V/∂θ[keys[k]] at every saved point -- the Jacobian of the voltage curve a
 least-squares fit of `keys` needs, from ONE ensemble call instead of 2 length(keys) + 1.  Constant / `:rest` inputs only; the states are bit for bit those of
 `simulate_ensemble`.  Derivatives are with respect to the absolute parameter value, at fixed time.
+`outputs` names the per-point channels differentiated (`plh_integrate_sens_out`): `:V` -> `dV_dθ`, `:I` -> `dI_dθ` (what a constant-voltage leg measures), `:T_avg` ->
+`dT_avg_dθ` (thermal models); each max_pts × n_sens × n, `nothing` when not asked for.
 """
-function simulate_ensemble_sens(m::Model, p, Θ::Matrix{Float64}, protocol, keys::Vector{Symbol}; SOC = p.opts.SOC, max_pts = 2048)
+function simulate_ensemble_sens(m::Model, p, Θ::Matrix{Float64}, protocol, keys::Vector{Symbol}; SOC = p.opts.SOC, max_pts = 2048, outputs = (:V,))
+    all(c -> c ∈ (:V, :I, :T_avg), outputs) || error("outputs: :V, :I, :T_avg")
     n = size(Θ, 1)
     runs = [make_run(p, s) for s in protocol]
     o = p.opts
@@ -267,16 +286,20 @@ function simulate_ensemble_sens(m::Model, p, Θ::Matrix{Float64}, protocol, keys
     npts = zeros(Cint, n); Y = zeros(m.N, n)
     info = Matrix{RunInfo}(undef, length(runs), n); cnt = Vector{Counters}(undef, n)
     Tavg = p.numerics.temperature ? zeros(max_pts, n) : Float64[]
-    dY = zeros(m.N, ns, n); dV = zeros(max_pts, ns, n); stat = zeros(Cint, 3, n)
-    GC.@preserve t V I S npts Y info cnt Tavg ts cols dY dV stat begin
+    dY = zeros(m.N, ns, n); stat = zeros(Cint, 3, n)
+    chan(c) = c ∈ outputs ? zeros(max_pts, ns, n) : nothing
+    dV, dI, dT = chan(:V), chan(:I), chan(:T_avg)
+    ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve t V I S npts Y info cnt Tavg ts cols dY dV dI dT stat begin
         out = Ref(Outputs(max_pts, pointer(t), pointer(V), pointer(I), pointer(S), isempty(Tavg) ? C_NULL : pointer(Tavg), pointer(npts), pointer(Y), C_NULL,
                           pointer(info), pointer(cnt), C_NULL, 0, C_NULL, C_NULL))
-        rc = ccall((:plh_integrate_sens, lib), Cint,
-                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Run}, Ref{Opts}, Ref{Outputs}, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
-                   m.h, n, Θt, soc, length(runs), runs, opts, out, ns, cols, dY, dV, stat, PLH_HOST, C_NULL)
-        check(rc, "plh_integrate_sens")
+        so = Ref(SensOutputs(pointer(dY), ptr(dV), ptr(dI), ptr(dT), pointer(stat)))
+        rc = ccall((:plh_integrate_sens_out, lib), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Run}, Ref{Opts}, Ref{Outputs}, Cint, Ptr{Cint}, Ref{SensOutputs}, Cint, Ptr{Cvoid}),
+                   m.h, n, Θt, soc, length(runs), runs, opts, out, ns, cols, so, PLH_HOST, C_NULL)
+        check(rc, "plh_integrate_sens_out")
     end
-    (t = t, V = V, I = I, SOC = S, T_avg = Tavg, n_pts = npts, Y = Y, run_info = info, counters = cnt, dY_dθ = dY, dV_dθ = dV, sens_stat = stat)
+    (t = t, V = V, I = I, SOC = S, T_avg = Tavg, n_pts = npts, Y = Y, run_info = info, counters = cnt, dY_dθ = dY, dV_dθ = dV, dI_dθ = dI, dT_avg_dθ = dT, sens_stat = stat)
 end
 
 """
@@ -314,6 +337,7 @@ function lsq(m::Model, ens, tq::Vector{Float64}, V_data::Array{Float64}; weights
     max_pts, n = size(ens.t)
     n_runs, n_q = size(ens.run_info, 1), length(tq)
     dV = hasproperty(ens, :dV_dθ) ? ens.dV_dθ : nothing
+    hasproperty(ens, :dY_dθ) && dV === nothing && error("this ensemble was run without the voltage sensitivities: outputs = (:V, ...)")
     ns = dV === nothing ? 0 : size(dV, 2)
     ns <= 8 || error("lsq takes at most 8 sensitivity rows per call")
     per_cell = ndims(V_data) == 2 || (weights !== nothing && ndims(weights) == 2)
@@ -333,6 +357,46 @@ function lsq(m::Model, ens, tq::Vector{Float64}, V_data::Array{Float64}; weights
                     m.h, n, n_runs, max_pts, ens.t, ens.n_pts, ens.run_info, ens.V, ns, p(dV), n_q, tq, p(y), p(w), per_cell ? 1 : 0, interp_bc == :extrapolate ? 1 : 0,
                     cost, p(grad), p(JtJ), p(res), status, PLH_HOST, C_NULL),
               "plh_lsq")
+    end
+    (cost = cost, grad = grad, JtJ = JtJ, resid = res, status = status)
+end
+
+"""
+    lsq_multi(m, ens, tq, channels; interp_bc = :interpolate, resid = false)
+
+The same objective summed over several measured channels in one pass (`plh_lsq_multi`): `channels` is a vector of `(field, data, weights)` with `field` one of `:V`, `:I`,
+`:T_avg` (at most 3), `data` and `weights` vectors of length n_q shared by all cells (`weights = nothing`: ones; a channel without a datum at a time gets weight 0 there).
+An ensemble of `simulate_ensemble_sens` must hold the sensitivities of every channel used (`outputs = (:V, :I)`).  Returns `(cost, grad, JtJ, resid, status)`; `resid` is a
+vector of n_q × n matrices, one per channel, or `nothing`.
+"""
+function lsq_multi(m::Model, ens, tq::Vector{Float64}, channels; interp_bc = :interpolate, resid = false)
+    interp_bc ∈ (:interpolate, :extrapolate) || error("Invalid interp_bc method.")
+    1 <= length(channels) <= 3 || error("lsq_multi takes 1 .. 3 channels")
+    max_pts, n = size(ens.t)
+    n_runs, n_q = size(ens.run_info, 1), length(tq)
+    sens = hasproperty(ens, :dY_dθ)
+    ns = sens ? size(ens.dY_dθ, 2) : 0
+    ns <= 8 || error("lsq_multi takes at most 8 sensitivity rows per call")
+    dname = Dict(:V => :dV_dθ, :I => :dI_dθ, :T_avg => :dT_avg_dθ)
+    curves = [getproperty(ens, c[1]) for c in channels]
+    dcurves = [sens ? getproperty(ens, dname[c[1]]) : nothing for c in channels]
+    any(d -> sens && d === nothing, dcurves) && error("a channel's sensitivities were not integrated: simulate_ensemble_sens(...; outputs = (...))")
+    ys = [Vector{Float64}(c[2]) for c in channels]
+    ws = [c[3] === nothing ? nothing : Vector{Float64}(c[3]) for c in channels]
+    all(y -> length(y) == n_q, ys) && all(w -> w === nothing || length(w) == n_q, ws) || error("data and weights must have length n_q")
+    res = resid ? [zeros(n_q, n) for _ in channels] : nothing
+    cost = zeros(n); status = zeros(Cint, n)
+    grad = ns > 0 ? zeros(ns, n) : nothing
+    JtJ = ns > 0 ? zeros(ns, ns, n) : nothing
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve curves dcurves ys ws res grad JtJ begin
+        ch = [LsqChannel(pointer(curves[c]), p(dcurves[c]), pointer(ys[c]), p(ws[c]), res === nothing ? Ptr{Cdouble}(C_NULL) : pointer(res[c])) for c in eachindex(channels)]
+        check(ccall((:plh_lsq_multi, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{RunInfo}, Cint, Ptr{LsqChannel}, Cint, Cint, Ptr{Cdouble}, Cint, Cint,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
+                    m.h, n, n_runs, max_pts, ens.t, ens.n_pts, ens.run_info, length(ch), ch, ns, n_q, tq, 0, interp_bc == :extrapolate ? 1 : 0,
+                    cost, p(grad), p(JtJ), status, PLH_HOST, C_NULL),
+              "plh_lsq_multi")
     end
     (cost = cost, grad = grad, JtJ = JtJ, resid = res, status = status)
 end

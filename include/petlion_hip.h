@@ -351,6 +351,24 @@ int plh_integrate(plh_model_t m, int n_cells, const double* theta, const double*
  * I, V, P, eta_p, dT, any number of runs, new solutions only; everything else is PLH_E_UNSUPPORTED.  ptr_kind PLH_HOST or PLH_DEVICE (the call is synchronous). */
 int plh_integrate_sens(plh_model_t m, int n_cells, const double* theta, const double* SOC0, int n_runs, const plh_run* runs, const plh_opts* opts,
                        const plh_outputs* out, int n_sens, const int* sens_cols, double* dY_dtheta, double* dV_dtheta, int* sens_stat, int ptr_kind, void* stream);
+/* The same call with every per-point sensitivity channel the step loop can write.  A constant-voltage or V = :hold run has the voltage as its INPUT (dV/dtheta is 0 or a
+ * constant there): the measured quantity of such a leg is the current; a thermocouple measures T_avg.
+ *   dI_dtheta[cell][k][max_pts]      d I / d theta_k (I in C-rate, as plh_outputs.I) at every saved point; 0 in a run whose input is a constant current or :rest, and at the
+ *                                    last point of a run that ended on a current bound (the derivative of the end state as simulate() returns it, like dV at a voltage bound)
+ *   dT_avg_dtheta[cell][k][max_pts]  d T_avg / d theta_k (K) at every saved point: the temperature weighting of plh_outputs.T_avg applied to s_k.  Thermal models only:
+ *                                    PLH_E_UNSUPPORTED on an isothermal model (T_avg is a constant of theta there; nothing is clamped or zero-filled)
+ * Layout, NaN cases (a cell whose protocol failed, the unknown bound cases from there on; rows past n_pts stay NaN) and the definition at saved / interpolated end points are
+ * dV_dtheta's.  Any member may be NULL, at least one of the four derivative arrays must be given.  Which channels are asked for does not change a bit of any other output:
+ * one kernel serves every combination.  plh_integrate_sens(..., dY, dV, stat, ...) is this call with {dY, dV, NULL, NULL, stat}. */
+typedef struct {
+  double* dY_dtheta;
+  double* dV_dtheta;
+  double* dI_dtheta;
+  double* dT_avg_dtheta;
+  int* sens_stat;
+} plh_sens_outputs;
+int plh_integrate_sens_out(plh_model_t m, int n_cells, const double* theta, const double* SOC0, int n_runs, const plh_run* runs, const plh_opts* opts,
+                           const plh_outputs* out, int n_sens, const int* sens_cols, const plh_sens_outputs* sens_out, int ptr_kind, void* stream);
 
 /* ---- compiled input closures.  The reference compiles the user's closure and its symbolic derivatives into its generated control-row functions
  * (differentiate_residual_func, scalar_residual.jl:231-416); the built-in kernels interpret the PLH_VAL_EXPR programs instead.  A closure library is csrc/variant_tu.hip compiled once
@@ -412,6 +430,34 @@ int plh_lsq(plh_model_t m, int n_cells, int n_runs, int max_pts, const double* t
             int n_q, const double* tq, const double* y, const double* w, int per_cell, int extrapolate,
             double* cost /* [n_cells] */, double* grad /* [n_cells][n_sens] */, double* JtJ /* [n_cells][n_sens][n_sens], full symmetric */,
             double* resid /* [n_cells][n_q] or NULL */, int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
+
+/* ---- the same objective over several measured channels in one pass: V in a current-controlled leg, I in a constant-voltage leg, T_avg from a thermocouple.  Channel c is a
+ * per-point curve and the rows of its per-point sensitivities (plh_integrate_sens_out: V / dV_dtheta, I / dI_dtheta, T_avg / dT_avg_dtheta), with data and weights of its own.
+ * With S_c and S_ck the resampled functions of channel c's curve and of row k of its dcurve, r_cq = w_cq (S_c(tq_q) - y_cq) and J_cqk = w_cq S_ck(tq_q):
+ *   cost   = 1/2 sum_c sum_q r_cq^2
+ *   grad_k = sum_c sum_q J_cqk r_cq
+ *   JtJ_kl = sum_c sum_q J_cqk J_cql
+ *   ch[c].resid[q] = r_cq
+ * Everything else is plh_lsq's: the splines, the run assignment, clamping / continuation, status, the w == 0 rule (per channel: a point with w_cq == 0 is not evaluated in
+ * channel c, its resid there is 0 and a NaN datum there is harmless, while the other channels still count that time), NaN containment (NaN in one channel's dcurve reaches grad and
+ * JtJ of that cell only), the chunking through PLH_RESAMPLE_WS_BYTES.  The channels share tq: a channel that was measured at other times gets weight 0 where it has no datum.
+ * The units of the channels differ; the weights carry 1 / sigma of each.  Within a lane the sums run queries outer, channels inner, in the order of ch[]; the bits do not depend
+ * on the chunking or the pointer kind, and with n_ch == 1 they are plh_lsq's (plh_lsq is this call with one channel).
+ * ch[n_ch] itself is HOST memory for every ptr_kind; the pointers in it follow ptr_kind.  y, w: [n_q] (per_cell = 0) or [n_cells][n_q] (1), for all channels alike.
+ * PLH_E_ARG, nothing clamped: plh_lsq's cases, n_ch outside 1 .. PLH_LSQ_MAX_CHANNELS, a NULL ch, a NULL curve or y in a channel, a dcurve whose NULL-ness does not
+ * match n_sens. */
+#define PLH_LSQ_MAX_CHANNELS 3
+typedef struct {
+  const double* curve;   /* [n_cells][max_pts] */
+  const double* dcurve;  /* [n_cells][n_sens][max_pts]; NULL iff n_sens == 0 */
+  const double* y;       /* [n_q] or [n_cells][n_q]; follows per_cell */
+  const double* w;       /* [n_q] or [n_cells][n_q]; may be NULL (= 1) */
+  double* resid;         /* [n_cells][n_q] or NULL */
+} plh_lsq_channel;
+int plh_lsq_multi(plh_model_t m, int n_cells, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info,
+                  int n_ch, const plh_lsq_channel* ch, int n_sens, int n_q, const double* tq, int per_cell, int extrapolate,
+                  double* cost /* [n_cells] */, double* grad /* [n_cells][n_sens] */, double* JtJ /* [n_cells][n_sens][n_sens], full symmetric */,
+                  int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
 
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);

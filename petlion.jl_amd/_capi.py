@@ -22,6 +22,7 @@ DSTATE = {"dc_s_p_max": 1, "dc_s_p_min": 2, "dc_s_n_max": 3, "dc_s_n_min": 4, "d
 VAL_CONST, VAL_HOLD, VAL_REST, VAL_TABLE, VAL_EXPR = 0, 1, 2, 3, 4
 CHEM_LCO, CHEM_NMC, CHEM_LGM50 = 0, 1, 2
 LSQ_MAX_SENS = 8
+LSQ_MAX_CHANNELS = 3
 FLAG_RUNNING, ERR_INIT, ERR_STALL, ERR_MAXITERS, ERR_OUTPUT_FULL = -1, -11, -12, -13, -14
 
 BOUND_FIELDS = ["V_max", "V_min", "SOC_max", "SOC_min", "T_max", "c_s_n_max", "I_max", "I_min", "eta_plating_min",
@@ -72,6 +73,14 @@ class Outputs(C.Structure):
                 ("n_sel", C.c_int), ("sel", C.POINTER(C.c_int)), ("Y_sel", C.c_void_p)]      # selected state ranges per saved point (plh_outputs.sel: host memory)
 
 
+class SensOutputs(C.Structure):            # plh_sens_outputs
+    _fields_ = [("dY_dtheta", C.c_void_p), ("dV_dtheta", C.c_void_p), ("dI_dtheta", C.c_void_p), ("dT_avg_dtheta", C.c_void_p), ("sens_stat", C.c_void_p)]
+
+
+class LsqChannel(C.Structure):             # plh_lsq_channel
+    _fields_ = [("curve", C.c_void_p), ("dcurve", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p), ("resid", C.c_void_p)]
+
+
 RUN_INFO_DTYPE = np.dtype([("flag", np.int32), ("iterations", np.int32), ("t_end", np.float64), ("V", np.float64),
                            ("I", np.float64), ("SOC", np.float64), ("T_avg", np.float64)], align=True)
 COUNTERS_DTYPE = np.dtype([(f, np.int64) for f in COUNTER_FIELDS] + [("cyc", np.int64, (8,))], align=True)
@@ -80,7 +89,7 @@ assert RUN_INFO_DTYPE.itemsize == C.sizeof(RunInfo) and COUNTERS_DTYPE.itemsize 
 EXPORTS = ["plh_model_create", "plh_model_destroy", "plh_register_grid_library", "plh_n_states", "plh_n_diff", "plh_n_theta", "plh_theta_key",
            "plh_theta_default", "plh_lds_bytes", "plh_n_sections", "plh_section", "plh_jac_pattern", "plh_jac_alg_pattern", "plh_last_error", "plh_build_info", "plh_device_count", "plh_abi_layout",
            "plh_initial_guess", "plh_residual", "plh_jacobian", "plh_linear_solve", "plh_linear_solve_refined", "plh_residual_diff", "plh_residual_alg",
-           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
+           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
            "plh_comm_unique_id", "plh_comm_create", "plh_comm_destroy", "plh_comm_rank", "plh_comm_size", "plh_ensemble_run"]
 
 
@@ -144,8 +153,10 @@ def load(path=None):
     lib.plh_closure_digest.argtypes = [i, C.POINTER(Run)]
     lib.plh_closure_digest.restype = C.c_ulonglong
     lib.plh_integrate_sens.argtypes = [vp, i, vp, vp, i, C.POINTER(Run), C.POINTER(Opts), C.POINTER(Outputs), i, vp, vp, vp, vp, i, vp]
+    lib.plh_integrate_sens_out.argtypes = [vp, i, vp, vp, i, C.POINTER(Run), C.POINTER(Opts), C.POINTER(Outputs), i, vp, C.POINTER(SensOutputs), i, vp]
     lib.plh_resample.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, i, vp]
     lib.plh_lsq.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, vp]
+    lib.plh_lsq_multi.argtypes = [vp, i, i, i, vp, vp, vp, i, C.POINTER(LsqChannel), i, i, vp, i, i, vp, vp, vp, vp, i, vp]
     _cache[path] = lib
     return lib
 

@@ -783,11 +783,26 @@ def simulate_b(sol, p, tf=1e6, **kw):
     return simulate(p, tf, sol=sol, **kw)
 
 
-def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, stream=None, max_points=None, keep_Y=False, keep_YP=True, sens=None, sections=None):
+# the per-point channels a sensitivity run can differentiate (simulate_ensemble(sens_outputs=...)) and a fit can use (EnsembleSolution.lsq): name -> the ensemble's array of
+# its sensitivities; the curve itself is the attribute of that name
+SENS_CHANNELS = {"V": "dV_dtheta", "I": "dI_dtheta", "T_avg": "dT_avg_dtheta"}
+
+
+def _sens_channels(sens_outputs):
+    names = [sens_outputs] if isinstance(sens_outputs, str) else list(sens_outputs)
+    for c in names:
+        if c not in SENS_CHANNELS:
+            raise ValueError("sens_outputs: %r is not one of %s" % (c, ", ".join(SENS_CHANNELS)))
+    return [c for c in SENS_CHANNELS if c in names]
+
+
+def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, stream=None, max_points=None, keep_Y=False, keep_YP=True, sens=None, sections=None, sens_outputs=("V",)):
     """one plh_integrate call; numpy in / numpy out (host pointers) or torch device tensors (device=True).
     keep_YP = False: YP_final is not requested (the reference keeps YP only with var_keep.YP; the kernel then does not store the previous point's YP per step).
     sections: ((start, len), ...) -> bufs["Y_sel"][cell, point, k]: only those entries of every saved state vector, packed in the order given (plh_outputs.sel / Y_sel).
-    sens: list of theta keys -> plh_integrate_sens, bufs["dY_dtheta"][cell, k, state], bufs["dV_dtheta"][cell, k, point], bufs["sens_stat"][cell, 3]."""
+    sens: list of theta keys -> plh_integrate_sens, bufs["dY_dtheta"][cell, k, state], bufs["dV_dtheta"][cell, k, point], bufs["sens_stat"][cell, 3].
+    sens_outputs: the per-point channels differentiated, of "V", "I", "T_avg" -> bufs["dV_dtheta"], bufs["dI_dtheta"], bufs["dT_avg_dtheta"] (plh_integrate_sens_out; ("V",) is
+    plh_integrate_sens itself)."""
     lib, h = p._lib, p._h
     n = theta.shape[0]
     N = p.N.tot
@@ -835,15 +850,23 @@ def _integrate(p, theta, SOC0, runs, o, Y_init=None, t_init=None, device=False, 
     if sens:
         cols = np.ascontiguousarray([p.θ_keys.index(k) for k in sens], dtype=np.int32)
         ns = len(cols)
+        chans = _sens_channels(sens_outputs)
         if device:
-            bufs["dY_dtheta"], bufs["dV_dtheta"], bufs["sens_stat"] = mk(n, ns, N), mk(n, ns, mp), mk(n, 3, dt=torch.int32)
+            bufs["dY_dtheta"], bufs["sens_stat"] = mk(n, ns, N), mk(n, 3, dt=torch.int32)
         else:
-            bufs["dY_dtheta"], bufs["dV_dtheta"], bufs["sens_stat"] = np.empty((n, ns, N)), np.empty((n, ns, mp)), np.zeros((n, 3), np.int32)
+            bufs["dY_dtheta"], bufs["sens_stat"] = np.empty((n, ns, N)), np.zeros((n, 3), np.int32)
+        for c in chans:
+            bufs[SENS_CHANNELS[c]] = mk(n, ns, mp) if device else np.empty((n, ns, mp))
         if Y_init is not None:
             raise ValueError("sensitivities are integrated for new solutions only")
         bufs["sens_keys"] = list(sens)
-        cap.check(lib, lib.plh_integrate_sens(h, n, cap.ptr(theta), cap.ptr(SOC0), len(runs), arr, C.byref(os_), C.byref(out), ns, cols.ctypes.data,
-                                              cap.ptr(bufs["dY_dtheta"]), cap.ptr(bufs["dV_dtheta"]), cap.ptr(bufs["sens_stat"]), kind, stream), "plh_integrate_sens")
+        if chans == ["V"]:
+            cap.check(lib, lib.plh_integrate_sens(h, n, cap.ptr(theta), cap.ptr(SOC0), len(runs), arr, C.byref(os_), C.byref(out), ns, cols.ctypes.data,
+                                                  cap.ptr(bufs["dY_dtheta"]), cap.ptr(bufs["dV_dtheta"]), cap.ptr(bufs["sens_stat"]), kind, stream), "plh_integrate_sens")
+        else:
+            so = cap.SensOutputs(cap.ptr(bufs["dY_dtheta"]), cap.ptr(bufs.get("dV_dtheta")), cap.ptr(bufs.get("dI_dtheta")), cap.ptr(bufs.get("dT_avg_dtheta")), cap.ptr(bufs["sens_stat"]))
+            cap.check(lib, lib.plh_integrate_sens_out(h, n, cap.ptr(theta), cap.ptr(SOC0), len(runs), arr, C.byref(os_), C.byref(out), ns, cols.ctypes.data, C.byref(so), kind, stream),
+                      "plh_integrate_sens_out")
     else:
         t_call = time.perf_counter()
         rc = lib.plh_integrate(h, n, cap.ptr(theta), cap.ptr(SOC0), cap.ptr(Y_init), cap.ptr(t_init), len(runs), arr, C.byref(os_), C.byref(out), kind, stream)
@@ -882,12 +905,14 @@ class ResampledEnsemble:
 
 
 class EnsembleFit:
-    """ens.lsq(t, V_data): the least-squares misfit of every cell's voltage curve against data (EnsembleSolution.lsq).  cost [cell]; grad [cell, k] and JtJ [cell, k, k] with
-    respect to the ensemble's `sens` keys (.keys), None for an ensemble run without them; resid [cell, n_q] when asked for, else None; status [cell]."""
+    """ens.lsq(t, V_data): the least-squares misfit of every cell's measured curves against data (EnsembleSolution.lsq).  cost [cell]; grad [cell, k] and JtJ [cell, k, k] with
+    respect to the ensemble's `sens` keys (.keys), None for an ensemble run without them; resid (the voltage channel), resid_I, resid_T_avg [cell, n_q] when asked for and
+    the channel was given, else None; channels: the names of the channels summed, in the order of the sums; status [cell]."""
 
-    def __init__(self, keys):
+    def __init__(self, keys, channels=("V",)):
         self.keys = list(keys)
-        self.cost = self.grad = self.JtJ = self.resid = self.status = None
+        self.channels = list(channels)
+        self.cost = self.grad = self.JtJ = self.resid = self.resid_I = self.resid_T_avg = self.status = None
 
 
 class EnsembleSolution:
@@ -911,6 +936,8 @@ class EnsembleSolution:
         self.call_ms = bufs.get("call_ms")      # wall time of the plh_integrate call itself (host pointers: includes the copies back)
         # forward parameter sensitivities (simulate_ensemble(..., sens=[keys])): [cell, k, state] at the end of the protocol, [cell, k, point] for the voltage
         self.dY_dtheta, self.dV_dtheta, self.sens_stat = bufs.get("dY_dtheta"), bufs.get("dV_dtheta"), bufs.get("sens_stat")
+        # the further per-point channels (sens_outputs=("V", "I", "T_avg")): [cell, k, point], None when not asked for
+        self.dI_dtheta, self.dT_avg_dtheta = bufs.get("dI_dtheta"), bufs.get("dT_avg_dtheta")
         self.keys = list(bufs.get("sens_keys") or [])      # the `sens` names, in the order of the k axis
 
     # With device=True the launch is asynchronous: the per-cell summaries stay in HBM until they are looked at (the first access synchronises),
@@ -995,28 +1022,39 @@ class EnsembleSolution:
                 v.record_stream(ext)
         return out
 
-    def lsq(self, t, V_data, weights=None, interp_bc="interpolate", resid=False):
-        """The weighted least-squares misfit of every cell's voltage curve against measured data on the device (plh_lsq; csrc/plh_lsq.h), and -- for an ensemble run with
-        sens=[keys] -- its gradient and Gauss-Newton matrix with respect to those keys: with S_V = ens(t).V and S_k the same spline through row k of dV_dtheta,
-        r = w (S_V(t) - V_data), J[:, k] = w S_k(t), cost = r.r / 2, grad = J'r, JtJ = J'J per cell (J at fixed knots: the saved times' dependence on the parameters is
-        ignored, as for every post-interpolated output).  t [n_q]; V_data and weights [n_q] (shared by all cells) or [n_cells, n_q]; weights = None: ones.  A point with
-        weight 0 is left out (a NaN time or datum there is harmless).  interp_bc as ens(t).  A device=True ensemble takes and returns torch tensors in HBM, queued on the
-        launch stream; a host ensemble numpy arrays.  Returns an EnsembleFit: .cost [n], .grad [n, k], .JtJ [n, k, k] (None without sens), .resid [n, n_q] (resid=True) or
-        None, .status [n] (1: the cell failed or was cut at max_points -- its rows are NaN), .keys."""
+    def lsq(self, t, V_data=None, weights=None, interp_bc="interpolate", resid=False, I_data=None, I_weights=None, T_avg_data=None, T_avg_weights=None):
+        """The weighted least-squares misfit of every cell's measured curves against data on the device (plh_lsq_multi; csrc/plh_lsq.h), and -- for an ensemble run with
+        sens=[keys] -- its gradient and Gauss-Newton matrix with respect to those keys.  Channels: the voltage (V_data, weights), the current (I_data, I_weights: what a
+        constant-voltage leg measures) and the average temperature (T_avg_data, T_avg_weights); at least one.  With S_c = ens(t).<channel> and S_ck the same spline through
+        row k of the channel's sensitivities (dV_dtheta, dI_dtheta, dT_avg_dtheta: simulate_ensemble(sens_outputs=...)), r_c = w_c (S_c(t) - data_c), J_c[:, k] = w_c S_ck(t):
+        cost = sum_c r_c.r_c / 2, grad = sum_c J_c'r_c, JtJ = sum_c J_c'J_c per cell (J at fixed knots: the saved times' dependence on the parameters is ignored, as for every
+        post-interpolated output).  t [n_q], shared by the channels (a channel without a datum at a time gets weight 0 there); data and weights [n_q] (shared by all cells) or
+        [n_cells, n_q]; weights None: ones.  A point with weight 0 is left out of its channel (a NaN time or datum there is harmless).  interp_bc as ens(t).  A device=True
+        ensemble takes and returns torch tensors in HBM, queued on the launch stream; a host ensemble numpy arrays.  Returns an EnsembleFit: .cost [n], .grad [n, k],
+        .JtJ [n, k, k] (None without sens), .resid / .resid_I / .resid_T_avg [n, n_q] (resid=True, per channel given) or None, .channels, .status [n] (1: the cell failed or
+        was cut at max_points -- its rows are NaN), .keys."""
         if interp_bc not in ("interpolate", "extrapolate"):
             raise ValueError("Invalid interp_bc method.")
         tq = np.ascontiguousarray(np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=np.float64))
         if tq.ndim != 1 or tq.size < 1:
             raise ValueError("t must be a 1-D array of measurement times")
+        given = [(c, d, w_) for c, d, w_ in (("V", V_data, weights), ("I", I_data, I_weights), ("T_avg", T_avg_data, T_avg_weights)) if d is not None]
+        if not given:
+            raise ValueError("ens.lsq needs the data of at least one channel: V_data, I_data or T_avg_data")
         n, mp = self.t.shape
-        ns = 0 if self.dV_dtheta is None else int(self.dV_dtheta.shape[1])
+        ns = len(self.keys)
         if ns > cap.LSQ_MAX_SENS:
             raise ValueError("ens.lsq takes at most %d sens keys per call (this ensemble has %d)" % (cap.LSQ_MAX_SENS, ns))
+        for c, _, _ in given:
+            if getattr(self, c, None) is None:
+                raise ValueError("this ensemble has no per-point %s" % c)
+            if ns and getattr(self, SENS_CHANNELS[c]) is None:
+                raise ValueError("%s_data: this ensemble was run without the sensitivities of %s; ask for them with simulate_ensemble(..., sens_outputs=(..., %r))" % (c, c, c))
         device = not isinstance(self.t, np.ndarray)
         if device:
             import torch
             dev = self.t.device
-            conv = lambda a: (a if hasattr(a, "device") else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
+            conv = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()      # (numpy 2 arrays have .device too)
             mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
             kind, stream, rinfo = cap.PLH_DEVICE, self._stream, self._run_info_raw
         else:
@@ -1027,29 +1065,34 @@ class EnsembleSolution:
         if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
             # data made or converted on torch's current stream are read on the launch stream: that stream waits for them, and the allocator learns of their use there
             ext = torch.cuda.ExternalStream(int(stream), device=dev)
-        y = conv(V_data)
-        w = None if weights is None else conv(weights)
-        for what, a in (("V_data", y), ("weights", w)):
-            if a is not None and tuple(a.shape) not in ((tq.size,), (n, tq.size)):
-                raise ValueError("%s must be [n_q] or [n_cells, n_q] = [%d] or [%d, %d], not %s" % (what, tq.size, n, tq.size, list(a.shape)))
-        per_cell = 1 if y.ndim == 2 or (w is not None and w.ndim == 2) else 0
-        if per_cell:                                            # (one form for both)
-            y = y if y.ndim == 2 else conv(y.expand(n, tq.size) if device else np.broadcast_to(y, (n, tq.size)))
-            w = w if w is None or w.ndim == 2 else conv(w.expand(n, tq.size) if device else np.broadcast_to(w, (n, tq.size)))
+        data = [[c, conv(d), None if w_ is None else conv(w_)] for c, d, w_ in given]
+        wname = {"V": "weights", "I": "I_weights", "T_avg": "T_avg_weights"}
+        for c, y, w in data:
+            for what, a in ((c + "_data", y), (wname[c], w)):
+                if a is not None and tuple(a.shape) not in ((tq.size,), (n, tq.size)):
+                    raise ValueError("%s must be [n_q] or [n_cells, n_q] = [%d] or [%d, %d], not %s" % (what, tq.size, n, tq.size, list(a.shape)))
+        per_cell = 1 if any(a is not None and a.ndim == 2 for _, y, w in data for a in (y, w)) else 0
+        if per_cell:                                            # (one form for every array of every channel)
+            full = lambda a: a if a is None or a.ndim == 2 else conv(a.expand(n, tq.size) if device else np.broadcast_to(a, (n, tq.size)))
+            data = [[c, full(y), full(w)] for c, y, w in data]
         if ext is not None:
             ext.wait_stream(torch.cuda.current_stream(dev))
-        out = EnsembleFit(self.keys)
+        out = EnsembleFit(self.keys, [c for c, _, _ in data])
         out.cost, out.status = mk(n), mk(n, dt=torch.int32 if device else np.int32)
         if ns:
             out.grad, out.JtJ = mk(n, ns), mk(n, ns, ns)
-        if resid:
-            out.resid = mk(n, tq.size)
+        rname = {"V": "resid", "I": "resid_I", "T_avg": "resid_T_avg"}
+        ch = (cap.LsqChannel * len(data))()
+        for q, (c, y, w) in enumerate(data):
+            if resid:
+                setattr(out, rname[c], mk(n, tq.size))
+            ch[q] = cap.LsqChannel(cap.ptr(getattr(self, c)), cap.ptr(getattr(self, SENS_CHANNELS[c])) if ns else None, cap.ptr(y), cap.ptr(w), cap.ptr(getattr(out, rname[c])))
         lib, h = self.p._lib, self.p._h
-        cap.check(lib, lib.plh_lsq(h, n, len(self.run_names), mp, cap.ptr(self.t), cap.ptr(self.n_pts), cap.ptr(rinfo), cap.ptr(self.V), ns, cap.ptr(self.dV_dtheta) if ns else None,
-                                   tq.size, tq.ctypes.data, cap.ptr(y), cap.ptr(w), per_cell, 1 if interp_bc == "extrapolate" else 0,
-                                   cap.ptr(out.cost), cap.ptr(out.grad), cap.ptr(out.JtJ), cap.ptr(out.resid), cap.ptr(out.status), kind, stream), "plh_lsq")
+        cap.check(lib, lib.plh_lsq_multi(h, n, len(self.run_names), mp, cap.ptr(self.t), cap.ptr(self.n_pts), cap.ptr(rinfo), len(data), ch, ns,
+                                         tq.size, tq.ctypes.data, per_cell, 1 if interp_bc == "extrapolate" else 0,
+                                         cap.ptr(out.cost), cap.ptr(out.grad), cap.ptr(out.JtJ), cap.ptr(out.status), kind, stream), "plh_lsq_multi")
         if ext is not None:
-            for v in (y, w, out.cost, out.grad, out.JtJ, out.resid, out.status):
+            for v in [a for _, y, w in data for a in (y, w)] + [out.cost, out.grad, out.JtJ, out.resid, out.resid_I, out.resid_T_avg, out.status]:
                 if v is not None:
                     v.record_stream(ext)
         return out
@@ -1097,7 +1140,7 @@ def make_protocol(p, protocol, n_cells=None):
     return runs, names
 
 
-def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, stream=None, max_points=None, outputs=None, YP=True, sens=None, initial_states=None, sections=None):
+def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, stream=None, max_points=None, outputs=None, YP=True, sens=None, initial_states=None, sections=None, sens_outputs=("V",)):
     """Integrate an ensemble of independent cells on this process's GPU.
 
     Theta: [n_cells, n_theta] array in `p.θ_keys` order (numpy = host memory; torch CUDA tensor with device=True = already in HBM).
@@ -1109,6 +1152,8 @@ def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, 
     YP = False: do not return YP of the final point (the reference's default: var_keep.YP is off unless :YP is among the outputs).
     sens = ["D_sp", "k_n", ...]: forward sensitivities with respect to these entries of θ next to the states (plh_integrate_sens): ens.dY_dtheta[cell, k, state] at the
     end of the protocol, ens.dV_dtheta[cell, k, point] at every saved point; the states and saved points are those of the call without `sens`.
+    sens_outputs = ("V", "I", "T_avg"): the per-point channels differentiated (default: the voltage only) -- "I" adds ens.dI_dtheta[cell, k, point], what a constant-voltage
+    leg measures; "T_avg" (thermal models) adds ens.dT_avg_dtheta[cell, k, point]; a channel not named is None.  ens.lsq fits against any of them.
     """
     n = Theta.shape[0]
     runs, names = make_protocol(p, protocol, n)
@@ -1135,7 +1180,7 @@ def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, 
             soc0 = np.ascontiguousarray((Y0[:, cs.start + n_p:cs.stop].mean(axis=1) / col("c_max_n") - col("θ_min_n")) / (col("θ_max_n") - col("θ_min_n")))
     sel, sel_ind = _resolve_sections(p, sections)
     bufs = _integrate(p, Theta, soc0, runs, o, Y_init=Y0, device=device, stream=stream, max_points=max_points,
-                      keep_Y=_wants_states(p, o.outputs if outputs is None else outputs), keep_YP=YP, sens=sens, sections=sel)
+                      keep_Y=_wants_states(p, o.outputs if outputs is None else outputs), keep_YP=YP, sens=sens, sections=sel, sens_outputs=sens_outputs)
     return EnsembleSolution(p, bufs, names, sel, sel_ind)
 
 

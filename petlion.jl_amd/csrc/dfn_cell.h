@@ -319,7 +319,10 @@ struct LaneRegs {
 // forward parameter sensitivities (dfn_sens.h): what plh_integrate hands the kernel
 struct SensArgs {               // (device pointers; part of IntegrateArgs)
   int n_sens;                   // number of theta columns differentiated (0: none)
-  const int* cols;              // [n_sens] 0-based positions in theta_keys
+  int chan;                     // (in what was padding: this struct is part of the argument block of EVERY kernel and keeps its size) the further per-point channels asked for:
+                                // SENS_CH_I dI/dtheta_k, SENS_CH_T dT_avg/dtheta_k (thermal models), each [n_cells][n_sens][max_pts] like dV.  Their pointers are not
+                                // kernel arguments: they follow the column list in device memory (sens_chan_ptrs), read by the GF_SENS instantiations where they store
+  const int* cols;              // [n_sens] 0-based positions in theta_keys; then, 8-byte aligned, double* dI, double* dT (meaningful where `chan` says so)
   const double* theta_pert;     // [n_cells][n_sens][P]: the cell's theta row with column cols[k] perturbed (relative 1e-7; built by plh_integrate)
   double* hist;                 // [n_cells][n_sens][MAXORD + 1][NPAD]: BDF history of every s_k
   double* dY;                   // [n_cells][n_sens][N] or nullptr: dY/dtheta_k at the end of the last completed run
@@ -332,6 +335,9 @@ struct SensArgs {               // (device pointers; part of IntegrateArgs)
   double* fsave; int fsave_stride;   // [n_cells][fsave_stride]: where a step that factors its own matrix parks the integrator's factorisation (dfn_sens.h, sens_factor_copy)
 };
 constexpr int SENS_CBAK = 384;
+constexpr int SENS_CH_I = 1, SENS_CH_T = 2;
+// where the channel pointers sit behind cols[n_sens] (ints): the host writes them there, the kernel reads them from there
+__host__ __device__ inline size_t sens_chan_offset(int n_sens) { return ((size_t)n_sens + 1) / 2 * 2; }
 
 __device__ __forceinline__ int lane_id() { return (int)threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return (int)threadIdx.x >> 6; }     // 0 for the one-wave kernels; 0 / 1 for M::W2

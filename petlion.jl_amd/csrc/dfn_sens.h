@@ -135,12 +135,24 @@ PL_DEV void sens_refactor(CellLDS<M>& S, LaneRegs& R, const double (&ypn)[M::NTR
   PL_XSYNC();
 }
 
-// dV/dtheta_k of the point just saved: S.delta holds s_k
+// dV/dtheta_k, dI/dtheta_k and dT_avg/dtheta_k of the point just saved: S.delta holds s_k.  Every lane must call it: the average temperature is a wave reduction (cellTavg), taken
+// before the lane-0 branch that stores; whether a channel was asked for is wave-uniform (a kernel argument).  The pointers of the two further channels are read here, from
+// behind the column list (SensArgs::cols), once per saved point and parameter: nothing more to keep in registers across the step.
 template <class M>
 PL_DEV void sens_put_V(CellLDS<M>& S, const SensCell<M>& X, int k, int idx) {
   PL_MODEL(M);
-  if (lane_id() == 0 && wave_id() == 0 && X.a.dV && idx >= 0 && idx < X.max_pts)
-    X.a.dV[((size_t)X.cell * X.a.n_sens + k) * X.max_pts + idx] = S.delta[O_PS] - S.delta[O_PS + NJ - 1];
+  const int chan = X.a.chan;
+  [[maybe_unused]] double sT = 0.0;
+  if constexpr (M::THERMAL) { if (chan & SENS_CH_T) sT = cellTavg<M>(S, S.delta); }
+  if (lane_id() == 0 && wave_id() == 0 && idx >= 0 && idx < X.max_pts) {
+    const size_t q = ((size_t)X.cell * X.a.n_sens + k) * X.max_pts + idx;
+    if (X.a.dV) X.a.dV[q] = S.delta[O_PS] - S.delta[O_PS + NJ - 1];
+    if (chan) {
+      double* const* cp = reinterpret_cast<double* const*>(X.a.cols + sens_chan_offset(X.a.n_sens));
+      if (chan & SENS_CH_I) cp[0][q] = S.delta[O_I];
+      if constexpr (M::THERMAL) { if (chan & SENS_CH_T) cp[1][q] = sT; }
+    }
+  }
 }
 
 // start of a run (after the consistent initialisation and ida_reinit: S.phi[0] = y0, S.yp = y'0, the algebraic block factored): s_k(t0), s'_k(t0) -> history
@@ -379,7 +391,8 @@ PL_DEV void sens_step(CellLDS<M>& S, LaneRegs& R, const IdaScalars& I, SensCell<
   PL_XSYNC();
 }
 
-// the point check_solve's first-step retry repeats (checks.jl:227-237): dV/dtheta of the point it repeats (hist[0] = s at the start of the run)
+// the point check_solve's first-step retry repeats (checks.jl:227-237): the per-point sensitivities of the point it repeats (hist[0] = s at the start of the run), through
+// S.delta like every other saved point -- the work vector is dead here as it is in sens_init: the integrator has been re-initialised and its next step starts from S.yy / S.yp
 template <class M>
 PL_DEV void sens_repeat_point(CellLDS<M>& S, const SensCell<M>& X, int idx) {
   PL_MODEL(M);
@@ -387,7 +400,9 @@ PL_DEV void sens_repeat_point(CellLDS<M>& S, const SensCell<M>& X, int idx) {
   for (int k = 0; k < X.a.n_sens; k++) {
     const double* h0 = X.hist(k, 0);
     PL_XSYNC();
-    if (lane == 0 && wave_id() == 0 && X.a.dV && idx >= 0 && idx < X.max_pts) X.a.dV[((size_t)X.cell * X.a.n_sens + k) * X.max_pts + idx] = h0[O_PS] - h0[O_PS + NJ - 1];
+    PL_VEC(n) S.delta[n] = h0[n];
+    PL_XSYNC();
+    sens_put_V(S, X, k, idx);
   }
   PL_XSYNC();
 }

@@ -792,7 +792,7 @@ static void launch_copy_words(hipStream_t st, const void* src, void* dst, size_t
 #endif
 }
 // forward parameter sensitivities of a plh_integrate_sens call (dfn_sens.h)
-struct SensReq { int n_sens; const int* cols; double* dY; double* dV; int* stat; };
+struct SensReq { int n_sens; const int* cols; double* dY; double* dV; int* stat; double* dI; double* dT; mutable double* d_dI; mutable double* d_dT; };      // (dI, dT: the further per-point channels of plh_integrate_sens_out; d_*: where the kernel writes them)
 // theta_pert[cell][k][:] = the cell's theta row with column cols[k] moved by a relative 1e-7 (an absolute 1e-7 where the entry is zero)
 __host__ __device__ inline void theta_pert_entry(const double* theta, const int* cols, int n_sens, int P, double* out, size_t q) {
   const int col = (int)(q % P), k = (int)((q / P) % n_sens); const size_t cell = q / ((size_t)P * n_sens);
@@ -899,10 +899,12 @@ static int check_opts(const plh_model_s* m, const plh_opts* opts) {
   return 0;
 }
 static int check_sens(const plh_model_s* m, const SensReq* sq, int n_runs, const plh_run* runs, const plh_opts* opts, const double* Y_init) {
-  if (sq->n_sens < 1 || sq->n_sens > 64 || !sq->cols || (!sq->dY && !sq->dV)) return fail(PLH_E_ARG, "plh_integrate_sens: 1 <= n_sens <= 64, theta columns and at least one of dY_dtheta / dV_dtheta");
+  if (sq->n_sens < 1 || sq->n_sens > 64 || !sq->cols || (!sq->dY && !sq->dV && !sq->dI && !sq->dT))
+    return fail(PLH_E_ARG, "plh_integrate_sens: 1 <= n_sens <= 64, theta columns and at least one of dY_dtheta / dV_dtheta");      // (plh_integrate_sens_out: or dI_dtheta / dT_avg_dtheta)
   for (int k = 0; k < sq->n_sens; k++) if (sq->cols[k] < 0 || sq->cols[k] >= m->P) return fail(PLH_E_ARG, "plh_integrate_sens: theta column out of range");
   if (Y_init) return fail(PLH_E_UNSUPPORTED, "plh_integrate_sens: sensitivities of a continued solution (Y_init) are not carried across calls");
   if (m->ops->w2) return fail(PLH_E_UNSUPPORTED, "plh_integrate_sens: one wavefront per cell only");
+  if (sq->dT && !m->ops->thermal) return fail(PLH_E_UNSUPPORTED, "plh_integrate_sens_out: dT_avg_dtheta needs a thermal model (T_avg does not depend on theta in an isothermal one)");
   if (opts->refine > 0 || opts->n_tdiscon > 0 || opts->n_stop > 0) return fail(PLH_E_UNSUPPORTED, "plh_integrate_sens: not with refine / tdiscon / a stop function");
   for (int r = 0; r < n_runs; r++)
     if ((runs[r].value_kind != PLH_VAL_CONST && runs[r].value_kind != PLH_VAL_REST && runs[r].value_kind != PLH_VAL_HOLD) || runs[r].mode == PLH_MODE_RES || runs[r].mode == PLH_MODE_DSTATE)
@@ -944,6 +946,8 @@ static std::vector<OutArr> output_table(const plh_model_s* m, size_t n, int n_ru
   if (sq) {
     const size_t ns = sq->n_sens;
     t.push_back({sq->dY, (void**)&a.sens.dY, W8 * ns * N, n, OC_SENS}); t.push_back({sq->dV, (void**)&a.sens.dV, W8 * ns * out->max_pts, n, OC_SENS});
+    // (the two further channels: their device pointers are not kernel arguments -- stage_sens puts them behind the column list, SensArgs::chan says which)
+    t.push_back({sq->dI, (void**)&sq->d_dI, W8 * ns * out->max_pts, n, OC_SENS}); t.push_back({sq->dT, (void**)&sq->d_dT, W8 * ns * out->max_pts, n, OC_SENS});
     t.push_back({sq->stat, (void**)&a.sens.stat, 3 * sizeof(int), n, OC_SENS});
   }
   return t;
@@ -1131,7 +1135,13 @@ static int stage_protocol(Stage& s, int n, int n_runs, const plh_run* runs, cons
 // the workspaces of a sensitivity request, the perturbed theta rows, and outputs that read as NaN (all-ones bytes) for cells that never get as far as writing them
 static int stage_sens(const plh_model_s* m, Stage& s, size_t n, size_t max_pts, const SensReq* sq, IntegrateArgs& a) {
   const size_t ns = sq->n_sens, NPAD = m->N + (m->N & 1);
-  a.sens.n_sens = (int)ns; a.sens.cols = s.in_host(sq->cols, ns);
+  // the column list, and behind it the pointers of the further channels (dfn_cell.h, sens_chan_offset)
+  std::vector<int> cols(pl::sens_chan_offset((int)ns) + 2 * sizeof(double*) / sizeof(int), 0);
+  std::copy(sq->cols, sq->cols + ns, cols.begin());
+  double* const chp[2] = {sq->d_dI, sq->d_dT};
+  memcpy(cols.data() + pl::sens_chan_offset((int)ns), chp, sizeof chp);
+  a.sens.n_sens = (int)ns; a.sens.cols = s.in_host(cols.data(), cols.size());
+  a.sens.chan = (sq->d_dI ? pl::SENS_CH_I : 0) | (sq->d_dT ? pl::SENS_CH_T : 0);
   double* tp = (double*)s.dev_block(n * ns * m->P * sizeof(double)); a.sens.hist = (double*)s.dev_block(n * ns * 6 * NPAD * sizeof(double));
   a.sens.cbak = (double*)s.dev_block(n * pl::SENS_CBAK * sizeof(double)); a.sens.aux = (double*)s.dev_block(n * ns * 4 * sizeof(double));
   a.sens.fsave_stride = m->ops->fsave_doubles;
@@ -1139,7 +1149,7 @@ static int stage_sens(const plh_model_s* m, Stage& s, size_t n, size_t max_pts, 
   CHECK_STAGE(s);
   a.sens.theta_pert = tp; launch_theta_pert(s.st, a.theta, a.sens.cols, (int)n, (int)ns, m->P, tp);
   if (a.sens.dY) HIPCHK(hipMemsetAsync(a.sens.dY, 0xff, n * ns * m->N * sizeof(double), s.st));
-  if (a.sens.dV) HIPCHK(hipMemsetAsync(a.sens.dV, 0xff, n * ns * max_pts * sizeof(double), s.st));
+  for (double* ch : {a.sens.dV, sq->d_dI, sq->d_dT}) if (ch) HIPCHK(hipMemsetAsync(ch, 0xff, n * ns * max_pts * sizeof(double), s.st));
   if (a.sens.stat) HIPCHK(hipMemsetAsync(a.sens.stat, 0, 3 * n * sizeof(int), s.st));
   if (a.sens.aux) HIPCHK(hipMemsetAsync(a.sens.aux, 0, n * ns * 4 * sizeof(double), s.st));
   return 0;
@@ -1218,14 +1228,22 @@ int plh_integrate(plh_model_t m, int n, const double* theta, const double* SOC0,
 int plh_integrate_sens(plh_model_t m, int n, const double* theta, const double* SOC0, int n_runs, const plh_run* runs, const plh_opts* opts, const plh_outputs* out,
                        int n_sens, const int* sens_cols, double* dY_dtheta, double* dV_dtheta, int* sens_stat, int kind, void* stream) {
   if (kind != PLH_HOST && kind != PLH_DEVICE) return fail(PLH_E_ARG, "plh_integrate_sens: ptr_kind must be PLH_HOST or PLH_DEVICE");
-  const SensReq sq = {n_sens, sens_cols, dY_dtheta, dV_dtheta, sens_stat};
+  const plh_sens_outputs so = {dY_dtheta, dV_dtheta, nullptr, nullptr, sens_stat};
+  return plh_integrate_sens_out(m, n, theta, SOC0, n_runs, runs, opts, out, n_sens, sens_cols, &so, kind, stream);
+}
+
+int plh_integrate_sens_out(plh_model_t m, int n, const double* theta, const double* SOC0, int n_runs, const plh_run* runs, const plh_opts* opts, const plh_outputs* out,
+                           int n_sens, const int* sens_cols, const plh_sens_outputs* so, int kind, void* stream) {
+  if (kind != PLH_HOST && kind != PLH_DEVICE) return fail(PLH_E_ARG, "plh_integrate_sens: ptr_kind must be PLH_HOST or PLH_DEVICE");
+  if (!so) return fail(PLH_E_ARG, "plh_integrate_sens_out: null plh_sens_outputs");
+  const SensReq sq = {n_sens, sens_cols, so->dY_dtheta, so->dV_dtheta, so->sens_stat, so->dI_dtheta, so->dT_avg_dtheta, nullptr, nullptr};
   return integrate_impl(m, n, theta, SOC0, nullptr, nullptr, n_runs, runs, opts, out, kind, stream, &sq);
 }
 
 // ---- plh_resample: one per-point field of an ensemble on a time grid shared by all cells (kernels and algorithm: plh_resample.h) ----
 // The slopes need a workspace of max_pts x width doubles per cell -- a second copy of the field.  It is kept per stream and bounded: the cells are processed in chunks
 // (successive launches on the stream) of at most PLH_RESAMPLE_WS_BYTES of workspace (environment, read at every call; default 256 MiB; never less than one cell).
-// (shared with plh_lsq, whose columns are V and the rows of dV_dtheta: cells per chunk -- `blocks_per_cell` of the widest launch bounds the grid -- and the chunk's workspace)
+// (shared with plh_lsq / plh_lsq_multi, whose columns are every channel's curve and the rows of its sensitivities: cells per chunk -- `blocks_per_cell` of the widest launch bounds the grid -- and the chunk's workspace)
 static int resample_work(StreamCtx& cx, int n, int n_runs, int max_pts, int n_q, int width, size_t blocks_per_cell, size_t* chunk_out, plrs::Work* w) {
   size_t budget = (size_t)256 << 20;
   if (const char* e = getenv("PLH_RESAMPLE_WS_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
@@ -1273,8 +1291,8 @@ int plh_resample(plh_model_t m, int n, int n_runs, int max_pts, const double* t,
   return 0;
 }
 
-// ---- plh_lsq: misfit of the voltage curves against data, gradient and Gauss-Newton matrix per cell (kernels: plh_lsq.h; the slopes of V and of the rows of dV_dtheta share
-// plh_resample's workspace and its chunking) ----
+// ---- plh_lsq / plh_lsq_multi: misfit of the measured curves against data, gradient and Gauss-Newton matrix per cell (kernels: plh_lsq.h; the slopes of every channel's curve
+// and of the rows of its sensitivities share plh_resample's workspace and its chunking).  plh_lsq is the one-channel call: one kernel, the same bits ----
 int plh_lsq(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, const double* V, int n_sens,
             const double* dV_dtheta, int n_q, const double* tq, const double* y, const double* w, int per_cell, int extrapolate,
             double* cost, double* grad, double* JtJ, double* resid, int* status, int kind, void* stream) {
@@ -1285,28 +1303,51 @@ int plh_lsq(plh_model_t m, int n, int n_runs, int max_pts, const double* t, cons
   if (!t || !n_pts || !run_info || !V || !tq || !y || !cost) return fail(PLH_E_ARG, "plh_lsq: null array (only w, resid and status may be NULL)");
   if ((n_sens > 0) != (dV_dtheta != nullptr) || (n_sens > 0) != (grad != nullptr) || (n_sens > 0) != (JtJ != nullptr))
     return fail(PLH_E_ARG, "plh_lsq: dV_dtheta, grad and JtJ are given with n_sens > 0 and NULL with n_sens == 0");
+  const plh_lsq_channel ch = {V, dV_dtheta, y, w, resid};
+  return plh_lsq_multi(m, n, n_runs, max_pts, t, n_pts, run_info, 1, &ch, n_sens, n_q, tq, per_cell, extrapolate, cost, grad, JtJ, status, kind, stream);
+}
+
+int plh_lsq_multi(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, int n_ch, const plh_lsq_channel* ch,
+                  int n_sens, int n_q, const double* tq, int per_cell, int extrapolate, double* cost, double* grad, double* JtJ, int* status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1 || n_runs < 1 || max_pts < 1 || n_q < 1) return fail(PLH_E_ARG, "plh_lsq_multi: n_cells, n_runs, max_pts and n_q must be >= 1");
+  if (n_sens < 0 || n_sens > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_lsq_multi: n_sens must be 0 .. PLH_LSQ_MAX_SENS (8)");
+  if (n_ch < 1 || n_ch > PLH_LSQ_MAX_CHANNELS || !ch) return fail(PLH_E_ARG, "plh_lsq_multi: n_ch must be 1 .. PLH_LSQ_MAX_CHANNELS (3), with the channel array");
+  if ((per_cell != 0 && per_cell != 1) || (extrapolate != 0 && extrapolate != 1)) return fail(PLH_E_ARG, "plh_lsq_multi: per_cell and extrapolate must be 0 or 1");
+  if (!t || !n_pts || !run_info || !tq || !cost) return fail(PLH_E_ARG, "plh_lsq_multi: null array (only w, resid and status may be NULL)");
+  if ((n_sens > 0) != (grad != nullptr) || (n_sens > 0) != (JtJ != nullptr)) return fail(PLH_E_ARG, "plh_lsq_multi: grad and JtJ are given with n_sens > 0 and NULL with n_sens == 0");
+  for (int c = 0; c < n_ch; c++) {
+    if (!ch[c].curve || !ch[c].y) return fail(PLH_E_ARG, "plh_lsq_multi: a channel without curve or y");
+    if ((n_sens > 0) != (ch[c].dcurve != nullptr)) return fail(PLH_E_ARG, "plh_lsq_multi: a channel's dcurve is given with n_sens > 0 and NULL with n_sens == 0");
+  }
   DeviceGuard guard(m->device);
   Stage s(m, kind, stream);
   StreamCtx& cx = *s.cx;
   const size_t pts = (size_t)n * max_pts, n_data = per_cell ? (size_t)n * n_q : (size_t)n_q, ns = (size_t)n_sens;
+  const int width = n_ch * (1 + n_sens);
   pllsq::Args A;
   plrs::Args& a = A.rs;
   a.t = s.in(t, pts); a.n_pts = s.in(n_pts, (size_t)n); a.run_info = s.in(run_info, (size_t)n * n_runs);
-  A.V = s.in(V, pts); A.dV = s.in(dV_dtheta, pts * ns); A.y = s.in(y, n_data); A.w = s.in(w, n_data);
-  A.cost = s.buf(cost, (size_t)n, false); A.grad = s.buf(grad, n * ns, false); A.JtJ = s.buf(JtJ, n * ns * ns, false); A.resid = s.buf(resid, (size_t)n * n_q, false);
+  for (int c = 0; c < PLH_LSQ_MAX_CHANNELS; c++) {
+    A.ch[c] = plh_lsq_channel{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (c < n_ch) A.ch[c] = plh_lsq_channel{s.in(ch[c].curve, pts), s.in(ch[c].dcurve, pts * ns), s.in(ch[c].y, n_data), s.in(ch[c].w, n_data), s.buf(ch[c].resid, (size_t)n * n_q, false)};
+  }
+  A.cost = s.buf(cost, (size_t)n, false); A.grad = s.buf(grad, n * ns, false); A.JtJ = s.buf(JtJ, n * ns * ns, false);
   a.status = s.buf(status, (size_t)n, false);
   CHECK_STAGE(s);
   if (int rc = cx.resample_tq.get(cx.st, std::vector<double>(tq, tq + n_q), &a.tq)) return rc;
   size_t chunk = 0;
-  if (int rc = resample_work(cx, n, n_runs, max_pts, n_q, 1 + n_sens, 1, &chunk, &a.w)) return rc;
-  a.n_runs = n_runs; a.max_pts = max_pts; a.width = 1 + n_sens; a.n_q = n_q; a.extrapolate = extrapolate; a.src = nullptr; a.dst = nullptr;
-  A.n_sens = n_sens; A.per_cell = per_cell;
+  if (int rc = resample_work(cx, n, n_runs, max_pts, n_q, width, 1, &chunk, &a.w)) return rc;
+  a.n_runs = n_runs; a.max_pts = max_pts; a.width = width; a.n_q = n_q; a.extrapolate = extrapolate; a.src = nullptr; a.dst = nullptr;
+  A.n_sens = n_sens; A.per_cell = per_cell; A.n_ch = n_ch;
   for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
     a.cell0 = (int)c0; a.n_chunk = (int)std::min(chunk, (size_t)n - c0);
     pllsq::launch_chunk(s.st, A);
   }
   FINISH(s);
-  s.back(cost, A.cost, (size_t)n); s.back(grad, A.grad, n * ns); s.back(JtJ, A.JtJ, n * ns * ns); s.back(resid, A.resid, (size_t)n * n_q); s.back(status, a.status, (size_t)n);
+  s.back(cost, A.cost, (size_t)n); s.back(grad, A.grad, n * ns); s.back(JtJ, A.JtJ, n * ns * ns);
+  for (int c = 0; c < n_ch; c++) s.back(ch[c].resid, A.ch[c].resid, (size_t)n * n_q);
+  s.back(status, a.status, (size_t)n);
   CHECK_STAGE(s);
   return 0;
 }

@@ -1,9 +1,10 @@
-// plh_lsq.h -- plh_lsq: the weighted least-squares misfit of every cell's voltage curve against measured data, its gradient and its Gauss-Newton matrix (include/petlion_hip.h
-// states the definition).  Like plh_resample.h: kernels over the saved points plh_integrate / plh_integrate_sens wrote, no model variant, host translation unit.
+// plh_lsq.h -- plh_lsq / plh_lsq_multi: the weighted least-squares misfit of every cell's measured curves (V; with plh_lsq_multi up to three channels: V, I, T_avg) against data,
+// its gradient and its Gauss-Newton matrix (include/petlion_hip.h states the definition).  Like plh_resample.h: kernels over the saved points plh_integrate / plh_integrate_sens wrote, no model variant, host translation unit.
 //
 // The curve S_V and the sensitivity rows S_k are plh_resample's functions, so k_resample_prep (status, run starts, elimination factors) and k_resample_locate (run, clamped
 // time and interval of every query) run unchanged; they read t, run_info and tq only.  Then one kernel:
-//   k_lsq_cell   one wave per cell over its 1 + n_sens columns (V, then the rows of dV_dtheta[cell]).  Every column is contiguous ALONG POINTS here (k_resample_field's columns
+//   k_lsq_cell   one wave per cell over its n_ch (1 + n_sens) columns, the channels side by side (channel c: its curve, then the rows of its dcurve[cell]; <= 27 columns, so the
+//                sweeps -- the serial part, lanes = columns -- of three channels take the time of one).  Every column is contiguous ALONG POINTS here (k_resample_field's columns
 //                are contiguous across columns), so the slopes are computed through an LDS tile of 64 consecutive points per column:
 //                  lanes = points    load a tile (one contiguous segment of <= 512 B per column, plus the two points the forward sweep looks ahead),
 //                  lanes = columns   sweep it in place (k_resample_field's arithmetic, operation for operation; the rows are padded to an odd stride: no two columns on a bank),
@@ -11,7 +12,7 @@
 //                forwards over a run's tiles (right-hand sides), then backwards (slopes).  A lane reloads from the workspace only what it stored itself; one
 //                workgroup barrier then hands the slopes to the lanes of the next phase.
 //                Then lanes = queries (q = lane, lane + 64, ...): the Hermite evaluation of every column, cost / grad / upper triangle of JtJ summed in registers in that
-//                order, a fixed-order butterfly over the wave, and lane 0 stores the cell's results: the bits do not depend on the chunking or the pointer kind.
+//                order (queries outer, channels inner: the 45 running sums are shared by the channels), a fixed-order butterfly over the wave, and lane 0 stores the cell's results: the bits do not depend on the chunking or the pointer kind.
 #pragma once
 
 #include "plh_resample.h"
@@ -21,27 +22,29 @@
 namespace pllsq {
 
 constexpr int NS = PLH_LSQ_MAX_SENS;      // sensitivity columns at most: a lane keeps 1 + NS + NS (NS + 1) / 2 sums
+constexpr int NCH = PLH_LSQ_MAX_CHANNELS; // channels at most
+constexpr int NCOL = NCH * (1 + NS);      // columns of a cell at most
 constexpr int TILE = plrs::TILE;          // points per tile = lanes
 constexpr int LD = TILE + 3;              // tile row: 64 points, 2 of look-ahead, 1 of padding (an odd stride in 8-byte words)
 
 struct Args {
-  plrs::Args rs;                            // as k_resample_prep / k_resample_locate take it (width = 1 + n_sens; src and dst unused)
-  int n_sens, per_cell;
-  const double* V; const double* dV;        // [n_cells][max_pts], [n_cells][n_sens][max_pts]
-  const double* y; const double* w;         // [n_q] or [n_cells][n_q]; w may be NULL
-  double* cost; double* grad; double* JtJ; double* resid;
+  plrs::Args rs;                            // as k_resample_prep / k_resample_locate take it (width = n_ch (1 + n_sens); src and dst unused)
+  int n_sens, per_cell, n_ch;
+  plh_lsq_channel ch[NCH];                  // (device pointers) curve [n_cells][max_pts], dcurve [n_cells][n_sens][max_pts]; y, w: [n_q] or [n_cells][n_q], w may be NULL; resid
+  double* cost; double* grad; double* JtJ;
 };
+// channel c's members without a dynamically indexed copy of the kernel argument (c is wave-uniform: scalar selects)
+#define PLLSQ_CH(A, c, member) ((c) == 0 ? (A).ch[0].member : (c) == 1 ? (A).ch[1].member : (A).ch[2].member)
 
 __global__ void __launch_bounds__(TILE) k_lsq_cell(Args A) {
-  __shared__ double T[1 + NS][LD];
+  __shared__ double T[NCOL][LD];
   const plrs::Args& a = A.rs;
   const int lc = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (lc >= a.n_chunk) return;
   const size_t cell = (size_t)a.cell0 + lc;
-  const int ns = A.n_sens, ncol = 1 + ns, nq = a.n_q;
-  double* resid = A.resid ? A.resid + cell * nq : nullptr;
+  const int ns = A.n_sens, nch = A.n_ch, cw = 1 + ns, ncol = nch * cw, nq = a.n_q;       // (cw: columns per channel)
   if (!a.w.ok[lc]) {                                                 // (none of its points is read)
-    if (resid) for (int q = lane; q < nq; q += TILE) resid[q] = plrs::rs_nan();
+    for (int c = 0; c < nch; c++) { double* rc = PLLSQ_CH(A, c, resid); if (rc) for (int q = lane; q < nq; q += TILE) rc[cell * nq + q] = plrs::rs_nan(); }
     for (int k = lane; k < ns; k += TILE) A.grad[cell * ns + k] = plrs::rs_nan();
     for (int k = lane; k < ns * ns; k += TILE) A.JtJ[cell * ns * ns + k] = plrs::rs_nan();
     if (lane == 0) A.cost[cell] = plrs::rs_nan();
@@ -51,7 +54,9 @@ __global__ void __launch_bounds__(TILE) k_lsq_cell(Args A) {
   const double* x = a.t + cell * a.max_pts;
   const double* fac = a.w.fac + (size_t)lc * a.max_pts * 2;
   double* sl = a.w.slope + (size_t)lc * ncol * a.max_pts;
-  auto ycol = [&](int c) { return c == 0 ? A.V + cell * a.max_pts : A.dV + (cell * ns + (c - 1)) * a.max_pts; };
+  // column j = channel j / cw, its curve (k = 0) or row k - 1 of its dcurve
+  auto chcol = [&](int c, int k) { return k == 0 ? PLLSQ_CH(A, c, curve) + cell * a.max_pts : PLLSQ_CH(A, c, dcurve) + (cell * ns + (k - 1)) * a.max_pts; };
+  auto ycol = [&](int j) { return chcol(j / cw, j % cw); };
   // lanes = points: rows [p0, p0 + cnt) of every column <-> the tile (cnt <= TILE + 2; the look-ahead points ride on lanes 0 and 1)
   auto load = [&](bool slopes, int p0, int cnt) {
     for (int c = 0; c < ncol; c++) {
@@ -121,8 +126,7 @@ __global__ void __launch_bounds__(TILE) k_lsq_cell(Args A) {
   // lanes = queries: they read slopes that other lanes stored to the workspace
   __syncthreads();
   const int* loc_i = a.w.loc_i + (size_t)lc * nq; const double* loc_t = a.w.loc_t + (size_t)lc * nq;
-  const double* yd = A.y + (A.per_cell ? cell * nq : 0);
-  const double* wd = A.w ? A.w + (A.per_cell ? cell * nq : 0) : nullptr;
+  const size_t d0 = A.per_cell ? cell * nq : 0;                      // the cell's row of y / w
   double cost = 0.0, G[NS], H[NS][NS];                               // H: the upper triangle
 #pragma unroll
   for (int k = 0; k < NS; k++) {
@@ -131,34 +135,37 @@ __global__ void __launch_bounds__(TILE) k_lsq_cell(Args A) {
     for (int l = k; l < NS; l++) H[k][l] = 0.0;
   }
   for (int q = lane; q < nq; q += TILE) {
-    const double wq = wd ? wd[q] : 1.0;
-    if (wq == 0.0) { if (resid) resid[q] = 0.0; continue; }          // left out: not evaluated
     const double tv = loc_t[q]; const int i = loc_i[q];
     const bool bad = !(tv == tv), one = i < 0;
     const int i0 = bad ? 0 : one ? ~i : i;
     double x0 = 0, x1 = 0, hh = 1, u = 0, ee = 0;
     if (!bad && !one) { x0 = x[i0]; x1 = x[i0 + 1]; hh = x1 - x0; u = tv - x0; ee = tv - x1; }
-    auto eval = [&](int c) {
+    auto eval = [&](int c, int k) {
       if (bad) return plrs::rs_nan();
-      const double* y = ycol(c);
+      const double* y = chcol(c, k);
       if (one) return y[i0];
-      const double* sc = sl + (size_t)c * a.max_pts;
+      const double* sc = sl + (size_t)(c * cw + k) * a.max_pts;
       const double y0 = y[i0], y1 = y[i0 + 1], s0 = sc[i0], s1 = sc[i0 + 1];
       const double d = (y1 - y0) / hh, c3 = (s0 + s1 - 2.0 * d) / (hh * hh);
       if (u <= -ee) return y0 + u * (s0 + u * ((3.0 * d - 2.0 * s0 - s1) / hh + u * c3));          // about the left node
       return y1 + ee * (s1 + ee * ((s0 + 2.0 * s1 - 3.0 * d) / hh + ee * c3));                     // about the right node
     };
-    const double rq = wq * (eval(0) - yd[q]);
-    if (resid) resid[q] = rq;
-    cost += rq * rq;
-    double J[NS];
+    for (int c = 0; c < nch; c++) {                                  // channels inner: one fixed order of the sums
+      const double* wd = PLLSQ_CH(A, c, w); double* resid = PLLSQ_CH(A, c, resid);
+      const double wq = wd ? wd[d0 + q] : 1.0;
+      if (wq == 0.0) { if (resid) resid[cell * nq + q] = 0.0; continue; }      // left out of this channel: not evaluated
+      const double rq = wq * (eval(c, 0) - PLLSQ_CH(A, c, y)[d0 + q]);
+      if (resid) resid[cell * nq + q] = rq;
+      cost += rq * rq;
+      double J[NS];
 #pragma unroll
-    for (int k = 0; k < NS; k++) J[k] = k < ns ? wq * eval(1 + k) : 0.0;
+      for (int k = 0; k < NS; k++) J[k] = k < ns ? wq * eval(c, 1 + k) : 0.0;
 #pragma unroll
-    for (int k = 0; k < NS; k++) if (k < ns) {
-      G[k] += J[k] * rq;
+      for (int k = 0; k < NS; k++) if (k < ns) {
+        G[k] += J[k] * rq;
 #pragma unroll
-      for (int l = k; l < NS; l++) if (l < ns) H[k][l] += J[k] * J[l];
+        for (int l = k; l < NS; l++) if (l < ns) H[k][l] += J[k] * J[l];
+      }
     }
   }
   // the wave's sums, in one order: every lane ends with the same bits

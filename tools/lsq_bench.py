@@ -10,7 +10,13 @@ Both timed with HIP events in the same process, alternating, median of --reps af
 recorded: the ratio to the sensitivity kernel's own time, the bytes that would otherwise cross to the host, and one finite-difference check made at reltol = abstol = 1e-8 on
 the first --fd-cells cells (measurement times up to the end of the shortest trajectory, and up to 0.9 of it): grad against central differences of cost over two extra plain
 runs per parameter and step (relative steps 1e-2, 1e-3, 1e-4; the yardstick is DESIGN.md 3's 7e-5 for
-dV/dtheta against differenced runs).  Writes the JSON at --out."""
+dV/dtheta against differenced runs).  Writes the JSON at --out.
+
+  python tools/lsq_bench.py --channels [--out profiles/lsq_channels.json]
+
+The `channels` record, same shard and times: (a) one fused V + I call (plh_lsq_multi, two channels) against two single-channel calls plus the torch additions of their cost,
+grad and JtJ, alternating in one process, HIP events, median of --reps after one warm-up, and the difference of the two results; (b) the sensitivity kernel's own time
+(plh_last_kernel_ms) with every channel of the model requested against dV/dtheta only, the same binary, alternating --reps times."""
 import argparse
 import copy
 import json
@@ -82,6 +88,50 @@ def measure(pkg, p, n, n_q, reps):
     return rec, keys
 
 
+def measure_channels(pkg, p, n, n_q, reps):
+    import torch
+    keys = [k for k in pkg.configs.SWEEP_KEYS if k in p.θ_keys]
+    cfg = pkg.configs.c4(p, n)
+    Th = torch.from_numpy(cfg["theta"]).cuda()
+    run = lambda outs: pkg.simulate_ensemble(p, Th, cfg["protocol"], SOC=cfg["SOC"], device=True, max_points=cfg["max_points"], sens=keys, sens_outputs=outs)
+    chans = ("V", "I", "T_avg") if p.temperature else ("V", "I")
+    ens = run(chans)                                                                                   # warm-up of the kernel, and the ensemble the lsq calls work on
+    torch.cuda.synchronize()
+    run(("V",)); torch.cuda.synchronize()
+    ms_all, ms_v = [], []
+    for _ in range(reps):                                                                              # (b) alternating: both see the same machine
+        e = run(chans); torch.cuda.synchronize(); ms_all.append(float(e.kernel_ms))
+        e = run(("V",)); torch.cuda.synchronize(); ms_v.append(float(e.kernel_ms))
+    t_end = float(ens.run_info["t_end"][:, -1].min())
+    tq = np.linspace(0.0, t_end, n_q)
+    rng = np.random.default_rng(0)
+    res = ens(tq, fields=("V", "I"))
+    dV = res.V[0] + torch.from_numpy(2e-3 * rng.standard_normal(n_q)).cuda()
+    dI = res.I[0] + torch.from_numpy(2e-3 * rng.standard_normal(n_q)).cuda()
+    wV, wI = torch.from_numpy(0.5 + rng.random(n_q)).cuda(), torch.from_numpy(0.5 + rng.random(n_q)).cuda()
+
+    def fused():
+        f = ens.lsq(tq, dV, weights=wV, I_data=dI, I_weights=wI)
+        return f.cost, f.grad, f.JtJ
+
+    def separate():
+        a, b = ens.lsq(tq, dV, weights=wV), ens.lsq(tq, I_data=dI, I_weights=wI)
+        return a.cost + b.cost, a.grad + b.grad, a.JtJ + b.JtJ
+
+    a, b = fused(), separate()
+    torch.cuda.synchronize()
+    agree = {nm: float(((x - y).abs().max() / y.abs().max()).cpu()) for nm, x, y in zip(("cost", "grad", "JtJ"), a, b)}
+    ms_f, ms_s = [], []
+    for _ in range(reps):
+        ms_f.append(timed(fused)[0])
+        ms_s.append(timed(separate)[0])
+    return {"cells": n, "n_q": n_q, "sens_keys": keys, "max_pts": int(ens.t.shape[1]),
+            "lsq": {"channels": ["V", "I"], "fused": spread(ms_f), "separate_calls_plus_torch_additions": spread(ms_s), "fused_over_separate": float(np.median(ms_f) / np.median(ms_s)),
+                    "max_abs_difference_over_max_abs": agree},
+            "sens_kernel": {"channels_all": list(chans), "all_channels": spread(ms_all), "dV_only": spread(ms_v), "all_over_dV_only": float(np.median(ms_all) / np.median(ms_v)),
+                            "against_the_parent_build": "not measured: no build of the parent commit on the box"}}
+
+
 def fd_check(pkg, p, keys, n, n_q, window=1.0, steps=(1e-2, 1e-3, 1e-4)):
     """grad of ens.lsq against central differences of cost: two plain runs per parameter and relative step, everything at reltol = abstol = 1e-8.  A difference quotient has
     its own error -- truncation at a large step (the voltage knee at the end of the discharge is strongly curved in the parameters), the runs' integration error over the
@@ -118,18 +168,26 @@ def fd_check(pkg, p, keys, n, n_q, window=1.0, steps=(1e-2, 1e-3, 1e-4)):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lsq.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--channels", action="store_true", help="the `channels` record (profiles/lsq_channels.json) instead of the plh_lsq one")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--points", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--fd-cells", type=int, default=16)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "lsq_channels.json" if a.channels else "lsq.json")
     import torch
     assert torch.cuda.is_available(), "lsq_bench.py needs a GPU"
     torch.cuda.init()                                      # (torch's runtime first, as in bench.py and smoke(): the library then joins the device torch opened)
     import pkgload
     pkg = pkgload.load()
     p = pkg.petlion(pkg.LCO)
+    if a.channels:
+        rec = {"channels": measure_channels(pkg, p, a.cells, a.points, a.reps)}
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(rec, open(a.out, "w"), indent=1)
+        print(json.dumps(rec))
+        return
     rec, keys = measure(pkg, p, a.cells, a.points, a.reps)
     rec = {"gpu": rec}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
