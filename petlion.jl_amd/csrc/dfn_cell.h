@@ -449,6 +449,18 @@ enum Phase { PH_RES, PH_JACFACT, PH_SOLVE, PH_NEWTVEC, PH_STEPCTL, PH_INIT, PH_O
 #ifndef PL_AMARK
 #define PL_AMARK(txt) do {} while (0)
 #endif
+// -DPL_PHASE_DETAIL=4 (with PL_PHASE_TIMERS): the two stretches of the step loop that no other timer covers -- slot 0: the head of ida_step up to ida_set_coeffs, slot 1: the loop
+// control of cell_simulate from the end of the output phase to the next ida_step.  Timers with a variable of their own (the second one lives across the loop's back edge);
+// nothing at all in every other build -- not even the fences of the thermal variants.
+#if defined(PL_PHASE_TIMERS) && !defined(PL_WAVE_EMU) && defined(PL_PHASE_DETAIL) && PL_PHASE_DETAIL == 4
+#define PL_TICH(v) long long v = (long long)__builtin_readcyclecounter()
+#define PL_RETICH(v) v = (long long)__builtin_readcyclecounter()
+#define PL_TOCH(S_, v, slot) do { if (threadIdx.x == 0) (S_).cyc[slot] += (long long)__builtin_readcyclecounter() - v; } while (0)
+#else
+#define PL_TICH(v) do {} while (0)
+#define PL_RETICH(v) do {} while (0)
+#define PL_TOCH(S_, v, slot) do {} while (0)
+#endif
 __host__ __device__ __forceinline__ int sec_of(int i) { return i < NP ? 0 : (i < NP + NS ? 1 : 2); }
 // ---- cross-lane primitives.  gfx950: DPP moves (probed on hardware, tools/probes/dpp_probe.hip: wave_shr:1 / wave_shl:1 shift
 // across the whole 64-lane wave, boundary lanes keep `old`), v_readlane for broadcasts.  Emulator: __shfl. ----

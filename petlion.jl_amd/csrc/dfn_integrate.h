@@ -67,6 +67,44 @@ constexpr bool PL_BRANCHY_PHI = false;
 // hides that -- the phase timers charged 2.2 k cycles per Newton iteration to the iterate / norm passes and 3.6 k per step to IDACompleteStep.  Cells are zero-initialised
 // (cell_setup) so that an order that has never been written is finite.
 template <class M> constexpr bool PL_FLAT = M::PHI_LDS > MAXORD && !M::W2;
+// The step boundary of the plain instantiation (F == 0) of those models: what follows an accepted step reads the accepted point out of the registers in which
+// ida_complete_step has just summed it instead of reading it back from LDS three times (SOC, save_pt, check_stop), the error weights of the next step are formed where
+// phi[0] is born instead of by a pass of their own at the head of the next ida_step, and the iterate that ida_nls used to form after convergence, which nothing reads, is
+// not formed.  Same operations on the same operands: every stored value and every decision is the one of the separate passes, bit for bit.
+// Only for the cells that run one per SIMD (petlion_kernels.h: PL_CELLS_PER_SIMD).  The small cells run two per SIMD on 256 registers each: the second wave hides the round
+// trips, and the values kept live instead went to scratch (quadratic particles 216 -> 260 B/lane, polynomial 20 -> 72): measured 4.5 % and 1 % SLOWER, so they keep the passes.
+// check_stop keeps its loops over S.yy / S.yp where they run: the c_s_n_max and c_e_min bounds when a run sets them (NaN = unset: not read), and the film growth of the
+// SEI models at every step; the vectors are stored by then.  What is gone are the reads of the six scalars every step looked at (StepPt).
+// -DPL_OLD_STEP_BOUNDARY compiles the separate passes for every instantiation: for the before / after comparisons of ONE source -- the emulator test builds of
+// tests/test_step_boundary_emu.py and the phase-timer builds of tools/phase_profile.py --old-boundary -- and for nothing else (no product build may carry it):
+#if defined(PL_OLD_STEP_BOUNDARY) && !defined(PL_WAVE_EMU) && !defined(PL_PHASE_TIMERS)
+#error "PL_OLD_STEP_BOUNDARY is for wave-emulator test builds and phase-timer profiling builds only"
+#endif
+constexpr size_t PL_TWO_CELLS_LDS_MAX = 26624;      // a cell of at most this many bytes of LDS leaves room for six on a CU: two cells per SIMD
+#ifdef PL_OLD_STEP_BOUNDARY
+template <int F, class M> constexpr bool PL_STEPB = false;
+#else
+template <int F, class M> constexpr bool PL_STEPB = F == 0 && PL_FLAT<M> && (sizeof(CellLDS<M>) > PL_TWO_CELLS_LDS_MAX);
+#endif
+// the entries of an accepted point (Y, YP) that the run logic looks at after every step; wave-uniform
+struct StepPt { double I, dI, V, dV, ep, dep; };
+// ... read from the LDS vectors (the point a run starts from, a step that ended on tstop: ida_get_solution)
+template <class M>
+__device__ __forceinline__ void step_pt_load(StepPt& pt, const double* Y, const double* YP) {
+  PL_MODEL(M);
+  pt.I = Y[O_I]; pt.dI = YP[O_I]; pt.V = Y[O_PS] - Y[O_PS + NJ - 1]; pt.dV = YP[O_PS] - YP[O_PS + NJ - 1];
+  pt.ep = Y[O_PS + NP] - Y[O_PE + NP + NS]; pt.dep = YP[O_PS + NP] - YP[O_PE + NP + NS];
+}
+// ... taken from the per-lane trips of a vector pass that holds y in `y` and y' in `yp` (entry n: trip n / 64 of lane n % 64; one-wave models)
+#define PL_TRIP_BCAST(v, n) lane_bcast((v)[(n) / WAVE], (n) % WAVE)
+template <class M>
+__device__ __forceinline__ void step_pt_regs(StepPt& pt, const double* y, const double* yp) {
+  PL_MODEL(M);
+  static_assert(!M::W2, "entry n lives in trip n / 64 of lane n % 64 only with one wave per cell");
+  pt.I = PL_TRIP_BCAST(y, O_I); pt.dI = PL_TRIP_BCAST(yp, O_I);
+  pt.V = PL_TRIP_BCAST(y, O_PS) - PL_TRIP_BCAST(y, O_PS + NJ - 1); pt.dV = PL_TRIP_BCAST(yp, O_PS) - PL_TRIP_BCAST(yp, O_PS + NJ - 1);
+  pt.ep = PL_TRIP_BCAST(y, O_PS + NP) - PL_TRIP_BCAST(y, O_PE + NP + NS); pt.dep = PL_TRIP_BCAST(yp, O_PS + NP) - PL_TRIP_BCAST(yp, O_PE + NP + NS);
+}
 #define PL_VEC(n) _Pragma("unroll") for (int k__ = 0; k__ < NTRIP; k__++) if (const int n = vrow<M>(k__, lane, wave_id()); vok<M>(k__, lane, wave_id()))
 // the same for statements that touch a vector in GLOBAL memory (NST entries: no padding there): always masked
 #define PL_VECG(n) _Pragma("unroll") for (int k__ = 0; k__ < NTRIP; k__++) if (const int n = vrow<M>(k__, lane, wave_id()); vokg<M>(k__, lane, wave_id()))
@@ -485,6 +523,10 @@ PL_DEV int ida_nls(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I, 
   // kernel, so each extra call site would be another copy of the node pass in the instruction stream of the hot loop.
   int jcur = 0, ret = 0, m = 0; bool done = false; double oldnrm = 0.0;
   for (bool first = true;; first = false) {
+    // (plain instantiation: nothing reads the iterate of the last correction.  Converged and accepted: ida_complete_step, or ida_get_solution when the step ended on
+    //  tstop, overwrites yy / yp; failed, by convergence or by the error test: ida_restore and the next form_iterate(first) do; the attempt after which ida_step gives up:
+    //  cell_simulate forms it, from the same predictor registers.  Every other instantiation reads it: run_input, the sensitivity step.)
+    if constexpr (PL_STEPB<F, M>) { if (done) break; }
     { PL_TIC(); form_iterate(S, I, first); PL_TOC(S, PH_NEWTVEC); }
     if (done) break;                                      // the iterate (yy, yp) now includes the last correction
     if constexpr ((F & GF_EXPR) != 0) { if (xrun) { value = closure_input(S, *xrun, I.tn, S.yy, S.yp); *xvalue = value; } }       // closure input: run.func(t, Y, YP, p) inside every residual (scalar_residual.jl:169-170)
@@ -610,8 +652,12 @@ PL_DEV void ida_restore(CellLDS<M>& S, IdaScalars& I, double saved_t) {
 // interpolates to tstop), IDAGetSolution(tn) is  y = phi[0]  and  y' = sum_j d_{j-1} phi[j]  (delt = 0 makes every c_j with j >= 1 vanish), i.e. by-products of the
 // running sums that update the history -- one pass over the history instead of two.  The coefficients d are formed by IDAGetSolution's own recurrence; y' is summed from the
 // top order down (IDAGetSolution sums upwards: last-bit differences in the REPORTED y' only -- the integrator continues from phi, not from y').
-template <class M>
-PL_DEV bool ida_complete_step(CellLDS<M>& S, IdaScalars& I, double err_k, double err_km1, double tstop) {
+// SB (PL_STEPB instantiations): the same pass also leaves the error weights of the next step in I.ew -- 1 / (rtol |phi[0]| + atol) from the sums it stores as phi[0]; phi[0] is
+// never rescaled (beta[0] = 1), so this is set_ewt's value -- and hands the entries of (y, y') that the run logic reads out of its registers (*pt; meaningless when the
+// step ended on tstop).
+template <class M, bool SB = false>
+PL_DEV bool ida_complete_step(CellLDS<M>& S, IdaScalars& I, double err_k, double err_km1, double tstop, [[maybe_unused]] double rtol = 0.0, [[maybe_unused]] double atol = 0.0,
+                              [[maybe_unused]] StepPt* pt = nullptr) {
   PL_MODEL(M);
   const int lane = lane_id();
   PL_AMARK("complete_step");
@@ -690,6 +736,10 @@ PL_DEV bool ida_complete_step(CellLDS<M>& S, IdaScalars& I, double err_k, double
       if (ku >= 3) { PL_VEC(n) S.phi[3][n] = q[3][k__]; } else if (grow && ku == 2) { PL_VEC(n) S.phi[3][n] = EE(n); }
       if (ku >= 2) { PL_VEC(n) S.phi[2][n] = q[2][k__]; } else if (grow) { PL_VEC(n) S.phi[2][n] = EE(n); }           // (ku == 1 here)
       PL_VEC(n) { S.phi[1][n] = q[1][k__]; S.phi[0][n] = acc[k__]; }
+      if constexpr (SB) {
+        PL_VEC(n) { const double w = pl_rcp(rtol * fabs(acc[k__]) + atol); I.ew[k__] = w; }
+        step_pt_regs<M>(*pt, acc, sp);
+      }
     } else if constexpr (PHI_REGS<M> && PL_BRANCHY_PHI) {      // (r03 form: what the thermal kernels are built with, -DPL_EXP_BRANCHY_PHI in petlion.jl_amd/buildflags.py, +2.5 % on C3)
       _Pragma("unroll") for (int j = MAXORD; j >= 0; j--) {
         if (j == ku + 1 && ku < I.maxord) { PL_VEC(n) PHI_WR(j, n, EE(n)); }
@@ -787,11 +837,14 @@ PL_DEV double next_tstop(const plh_opts& o, double t, bool continuation, double 
 // one IDASolve(ONE_STEP_TSTOP) call: advances, returns y(tret), y'(tret) in S.yy / S.yp.  0 ok, <0 failure
 template <int F, class M>
 PL_DEV int ida_step(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I, double tstop, double& tret, int mode, double& value,
-                               const plh_opts& o, Counters& cnt, const plh_run* frun = nullptr, GenRow* g = nullptr) {
+                               const plh_opts& o, Counters& cnt, const plh_run* frun = nullptr, GenRow* g = nullptr, [[maybe_unused]] StepPt* pt = nullptr) {
+  // (pt, PL_STEPB instantiations: the entries of the returned point that the run logic reads -- out of ida_complete_step's registers, or from S.yy / S.yp where
+  //  ida_get_solution has produced the point)
   PL_MODEL(M);
   const int lane = lane_id();
   const double uround = 2.220446049250313e-16;
   I.rtol = o.reltol; I.atol = o.abstol;
+  PL_TICH(pl_th__);
   if (I.nst == 0) {
     set_ewt(S, I, o.reltol, o.abstol);
     const double tdist = fabs(tstop - I.tn);
@@ -809,12 +862,18 @@ PL_DEV int ida_step(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I,
     PL_SYNC();
   } else {
     const double troundoff = 100.0 * uround * (fabs(I.tn) + fabs(I.hh));
-    if (fabs(I.tn - tstop) <= troundoff) { ida_get_solution(S, I, tstop, S.yy, S.yp); tret = tstop; return 0; }
+    if (fabs(I.tn - tstop) <= troundoff) {
+      ida_get_solution(S, I, tstop, S.yy, S.yp); tret = tstop;
+      if constexpr (PL_STEPB<F, M>) step_pt_load<M>(*pt, S.yy, S.yp);
+      return 0;
+    }
     if ((I.tn + I.hh - tstop) * I.hh > 0.0) I.hh = (tstop - I.tn) * (1.0 - 4.0 * uround);
-    set_ewt(S, I, o.reltol, o.abstol);
+    // (PL_STEPB: I.ew is already the weight vector of phi[0] -- the ida_complete_step that stored this phi[0] formed it; nothing between two steps writes phi[0] or I.ew)
+    if constexpr (!PL_STEPB<F, M>) set_ewt(S, I, o.reltol, o.abstol);
   }
   const double saved_t = I.tn; int ncf = 0, nef = 0; double err_k = 0, err_km1 = 0;
   if (I.nst == 0) { I.kk = 1; I.kused = 0; I.hused = 0.0; if (lane == 0 && wave_id() == 0) S.ida_psi[0] = I.hh; I.cj = 1.0 / I.hh; I.phase = 0; I.ns = 0; PL_XSYNC(); }
+  PL_TOCH(S, pl_th__, 0);
   for (;;) {
     double ck; { PL_TIC(); PL_TICE(3); ck = ida_set_coeffs(S, I); PL_TOC(S, PH_STEPCTL); PL_TOCE(S, 3, 0); }
     if constexpr ((F & GF_FUNC) != 0) { if (frun && frun->mode != PLH_MODE_DSTATE) value = run_input<F>(S, *frun, I.tn, S.yy, S.yp); }                           // every residual of this step attempt is evaluated at t = tn
@@ -848,9 +907,13 @@ PL_DEV int ida_step(CellLDS<M>& S, LaneRegs& R, const Tables* tb, IdaScalars& I,
   if (getenv("PL_EMU_TRACE") && lane == 0 && blockIdx.x == 0) fprintf(stderr, "dev step %d tn %.9g h %.6g k %d knew %d phase %d ns %d err_k %.6e err_km1 %.6e nef %d ncf %d\n", I.nst + 1, I.tn, I.hh, I.kk, I.knew, I.phase, I.ns, err_k, err_km1, nef, ncf);
 #endif
   PL_TIC(); PL_TICE(3);
-  const bool have_sol = ida_complete_step(S, I, err_k, err_km1, tstop);
+  const bool have_sol = ida_complete_step<M, PL_STEPB<F, M>>(S, I, err_k, err_km1, tstop, o.reltol, o.abstol, pt);
   PL_TOCE(S, 3, 2);
-  if (!have_sol) { ida_get_solution(S, I, tstop, S.yy, S.yp); tret = tstop; PL_TOC(S, PH_STEPCTL); PL_TOCE(S, 3, 3); return 0; }      // the step ended on tstop (|tn - tstop| <= troundoff)
+  if (!have_sol) {                                                                  // the step ended on tstop (|tn - tstop| <= troundoff)
+    ida_get_solution(S, I, tstop, S.yy, S.yp); tret = tstop;
+    if constexpr (PL_STEPB<F, M>) step_pt_load<M>(*pt, S.yy, S.yp);
+    PL_TOC(S, PH_STEPCTL); PL_TOCE(S, 3, 3); return 0;
+  }
   if ((I.tn + I.hh - tstop) * I.hh > 0.0) I.hh = (tstop - I.tn) * (1.0 - 4.0 * uround);
   tret = I.tn;                                                                      // y(tn), y'(tn) are in S.yy / S.yp (ida_complete_step)
   PL_TOC(S, PH_STEPCTL); PL_TOCE(S, 3, 3);
@@ -872,7 +935,8 @@ __device__ __forceinline__ double cellTavg(const CellLDS<M>& S, const double* Y)
 
 template <int F = 0, class M>
 PL_DEV void check_stop(CellLDS<M>& S, const plh_run& run, const plh_opts& o, double t, double tf, const double* Y, const double* YP,
-                                  double SOC, PrevVals& pv, int& flag) {
+                                  double SOC, PrevVals& pv, int& flag, [[maybe_unused]] const StepPt* pt = nullptr) {
+  // (pt, PL_STEPB instantiations after an accepted step: the entries of Y / YP that the tests of every step look at, already in registers)
   PL_MODEL(M);
   const double eps = t < 1.0 ? o.reltol : 0.0;
   [[maybe_unused]] double Tav = 0.0, dTav = 0.0;
@@ -881,7 +945,9 @@ PL_DEV void check_stop(CellLDS<M>& S, const plh_run& run, const plh_opts& o, dou
   // is loaded here, together; r05 loaded each where its test used it: ten dependent LDS round trips per step (1.5 k cycles by the phase timers for a dozen comparisons)
   const plh_bounds& b = run.bounds;
   double bImax = b.I_max, bImin = b.I_min, bVmin = b.V_min, bVmax = b.V_max, bSmin = b.SOC_min, bSmax = b.SOC_max, bcs = b.c_s_n_max, bce = b.c_e_min;
-  double bep = b.eta_plating_min, Ic = Y[O_I], dI = YP[O_I], V = cellV<M>(Y), dV = cellV<M>(YP), ep = Y[O_PS + NP] - Y[O_PE + NP + NS], dep = YP[O_PS + NP] - YP[O_PE + NP + NS];
+  double bep = b.eta_plating_min, Ic, dI, V, dV, ep, dep;
+  if (PL_STEPB<F, M> && pt) { Ic = pt->I; dI = pt->dI; V = pt->V; dV = pt->dV; ep = pt->ep; dep = pt->dep; }
+  else { Ic = Y[O_I]; dI = YP[O_I]; V = cellV<M>(Y); dV = cellV<M>(YP); ep = Y[O_PS + NP] - Y[O_PE + NP + NS]; dep = YP[O_PS + NP] - YP[O_PE + NP + NS]; }
   [[maybe_unused]] double bTmax = M::THERMAL ? b.T_max : 0.0;
   const int rmode = run.mode, vkind = run.value_kind;
   pl_pin(bImax, bImin, bVmin, bVmax, bSmin, bSmax, bcs, bce); pl_pin(bep, Ic, dI, V, dV, ep, dep, bTmax);
@@ -997,6 +1063,11 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
     const double val = lane == 0 ? tt : (lane == 1 ? Vv : (lane == 2 ? Iv : (lane == 3 ? soc : Tav)));
     if (outp && idx < out.max_pts) outp[idx] = val;
   };
+  // the same with V and I of the point already in registers (PL_STEPB instantiations: isothermal, per-step scalars only)
+  [[maybe_unused]] auto save_pt_regs = [&](int idx, double tt, const StepPt& pt, double soc) {
+    const double val = lane == 0 ? tt : (lane == 1 ? pt.V : (lane == 2 ? pt.I : (lane == 3 ? soc : T0)));
+    if (outp && idx < out.max_pts) outp[idx] = val;
+  };
   for (int r = 0; r < n_runs; r++) {
     // the run descriptor is staged in LDS once per run: reading it from global memory in every step costs ~1.4 k cycles per step (scalar
     // loads that cannot be hoisted past the global stores), and a by-value register copy proved fragile under register pressure
@@ -1076,6 +1147,12 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
     PrevVals pv; pv.frac = 1.0; pv.V = -1; pv.SOC = -1; pv.I = -1; pv.c_s_n = -1; pv.c_e_min = -1; pv.eta_pl = -1; pv.dfilm = -1; pv.T = -1; pv.g = -1;
     double tprev = 0.0, t = 0.0, t_prev_saved = t0; int iter = 1; bool stalled_once = false;
     double I_prev_pt = 0.0, t_restart = 0.0;
+    [[maybe_unused]] StepPt spt;                                        // (PL_STEPB: the accepted point's entries, out of ida_step)
+#if defined(PL_WAVE_EMU) && !defined(PL_OLD_STEP_BOUNDARY)
+    // (tests/test_step_boundary_emu.py compares this build with the -DPL_OLD_STEP_BOUNDARY one: the gate reads sizeof(CellLDS<M>), which the host compiler lays out --
+    //  a 301-state cell that fell under the threshold here would make that test compare the old boundary with itself)
+    static_assert(!(F == 0 && PL_FLAT<M> && M::NST >= 301) || PL_STEPB<F, M>, "emulator build: the plain kernel of a 301-state model must take the new step boundary");
+#endif
     [[maybe_unused]] double soc_nm1_s = 0.0, dt_step_s = 0.0, soc_n_s = 0.0;      // (sensitivities: the trapezoid SOC at the last two accepted points and the step between them)
     bool first_init = true, again = false, init_failed = false;
     [[maybe_unused]] int steps_since_restart = 2;                       // (accepted steps since a check_reinitialization! restart; 2 = "more than one")
@@ -1105,6 +1182,7 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
     bool init_ok = true;
     [[maybe_unused]] bool need_init = true;
     if constexpr ((F & GF_FUNC) == 0) init_ok = init_block();
+    PL_TICH(pl_tl__);
     while (init_ok && flag == PLH_FLAG_RUNNING) {
       if constexpr ((F & GF_FUNC) != 0) {
         if (need_init) { need_init = false; if (!init_block()) break; if (flag != PLH_FLAG_RUNNING) break; }      // (a bound can fire on the point the run starts from)
@@ -1116,7 +1194,8 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
       // two waves per cell: both evaluate the stop checks, SOC and I_prev_pt from S.yy redundantly; the wave that is ahead must not start overwriting S.yy (predictor of
       // the next step) while the other still reads the accepted point -- with a varying current its SOC, hence its stop flag, would differ
       if constexpr (M::W2) __syncthreads();
-      const int sf = ida_step<F>(S, R, tb, I, tstop_now, tret, mode, value, o, cnt, (is_tab || dstate) ? &run : nullptr, &grow);
+      PL_TOCH(S, pl_tl__, 1);
+      const int sf = ida_step<F>(S, R, tb, I, tstop_now, tret, mode, value, o, cnt, (is_tab || dstate) ? &run : nullptr, &grow, &spt);
       if (sf != 0) {
         if (I.nst == 0 && !stalled_once) {                              // check_solve, checks.jl:227-237
           stalled_once = true;
@@ -1130,18 +1209,25 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
           check_stop<F>(S, run, o, t, run.tf, S.yy, S.yp, SOC, pv, flag);
           continue;
         }
+        // (PL_STEPB: the run ends on the iterate of the attempt ida_step gave up after -- Y_final, run_info -- which ida_nls no longer forms: predictor registers + correction,
+        //  exactly its form_iterate(false))
+        if constexpr (PL_STEPB<F, M>) { static_assert(!PL_STEPB<F, M> || M::PRED_REGS, "the predictor of the last attempt must still be in registers"); form_iterate(S, I, false); }
         flag = sf; break;
       }
       iter++; t = tret;
       if constexpr ((F & GF_FUNC) != 0) steps_since_restart++;
       PL_TIC(); PL_TICE(3);
-      const double SOC_new = SOC + pl_div(0.5 * ((t + t0) - t_prev_saved) * (S.yy[O_I] + I_prev_pt), 3600.0);   // calc_SOC, scalar_residual.jl:103-111
+      double I_pt;                                                      // Y[O_I] of the accepted point
+      if constexpr (PL_STEPB<F, M>) I_pt = spt.I; else I_pt = S.yy[O_I];
+      const double SOC_new = SOC + pl_div(0.5 * ((t + t0) - t_prev_saved) * (I_pt + I_prev_pt), 3600.0);   // calc_SOC, scalar_residual.jl:103-111
       [[maybe_unused]] const double dt_saved = (t + t0) - t_prev_saved, soc_before = SOC;
       if constexpr ((F & GF_SENS) != 0) { soc_nm1_s = soc_before; dt_step_s = dt_saved; }
       SOC = SOC_new;
-      save_pt(nout, t + t0, S.yy, SOC); nout++;
+      if constexpr (PL_STEPB<F, M>) save_pt_regs(nout, t + t0, spt, SOC); else save_pt(nout, t + t0, S.yy, SOC);
+      nout++;
       PL_TOCE(S, 3, 4);
-      check_stop<F>(S, run, o, t, run.tf, S.yy, S.yp, SOC, pv, flag);
+      if constexpr (PL_STEPB<F, M>) check_stop<F>(S, run, o, t, run.tf, S.yy, S.yp, SOC, pv, flag, &spt);
+      else check_stop<F>(S, run, o, t, run.tf, S.yy, S.yp, SOC, pv, flag);
       PL_TOCE(S, 3, 5);
       if constexpr ((F & GF_SENS) != 0) sens_step(S, R, I, SX, mode, value, nout - 1, dt_saved);      // (the solution point in S.yy / S.yp is saved and restored around it)
       if (!is_fun && t == tprev) { flag = PLH_ERR_STALL; break; }      // (run_function has no stall test, checks.jl:251-269; run_residual -- res, dT, d<state> -- has: checks.jl:226)
@@ -1149,7 +1235,8 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
       if (nout >= out.max_pts && out.max_pts > 0 && flag == PLH_FLAG_RUNNING) { flag = PLH_ERR_OUTPUT_FULL; break; }
       if (flag == PLH_FLAG_RUNNING) {
         if (YPfin) { PL_VECG(n) YPprev[n] = S.yp[n]; }                // fire-and-forget: read back only when a bound fires (wave-uniform condition)
-        t_prev_saved = t + t0; I_prev_pt = S.yy[O_I];
+        t_prev_saved = t + t0;
+        if constexpr (PL_STEPB<F, M>) I_prev_pt = spt.I; else I_prev_pt = S.yy[O_I];
         if constexpr ((F & GF_FUNC) != 0) if (is_fun && t - tprev < 1e-3 * o.reltol) {                    // check_reinitialization!, checks.jl:341-364
           const double t_new = t + o.reltol, v_new = run_input<F>(S, run, t_new, S.yy, S.yp);
           const double big = fabs(value) > fabs(v_new) ? fabs(value) : fabs(v_new);
@@ -1164,6 +1251,7 @@ PL_DEV void cell_simulate(CellLDS<M>& S, LaneRegs& R, const Tables* tb, double S
         }
       }
       PL_TOC(S, PH_OUTPUT); PL_TOCE(S, 3, 6);
+      PL_RETICH(pl_tl__);
       if constexpr ((F & GF_FUNC) != 0) { if (again) need_init = true; }         // back to the consistent initialisation at t_restart
     }
     if (init_failed) { if (lane == 0) info[r] = ri; for (int q = r + 1; q < n_runs; q++) if (lane == 0) { plh_run_info z = ri; z.flag = PLH_FLAG_RUNNING; info[q] = z; } break; }

@@ -23,7 +23,7 @@ namespace pl {
 // of <= 26 624 B leaves room for at least six on a CU: those kernels are compiled for TWO cells per SIMD (256 registers per lane).  Measured r05:
 // quadratic particles (20.7 kB, 7 cells per CU) +42 %, polynomial +39 %, the (2, 2, 2, 10) grid (12.2 kB, 8 per CU) +63 %; three per SIMD +25 % only (168 registers).  The
 // 301-state models got that small only with the BDF history in global memory and lost 5 % there (measured, then removed: DESIGN.md 2): they stay at one.
-#define PL_CELLS_PER_SIMD(M) ((sizeof(CellLDS<M>) <= 26624 && !M::W2) ? 2 : 1)
+#define PL_CELLS_PER_SIMD(M) ((sizeof(CellLDS<M>) <= PL_TWO_CELLS_LDS_MAX && !M::W2) ? 2 : 1)      /* (PL_TWO_CELLS_LDS_MAX = 26 624 B: dfn_integrate.h, which gates the step boundary on it) */
 #define PL_ONE_WAVE_PER_SIMD __attribute__((amdgpu_waves_per_eu(M::NWAVES * PL_CELLS_PER_SIMD(M), M::NWAVES * PL_CELLS_PER_SIMD(M))))
 #else
 #define PL_ONE_WAVE_PER_SIMD

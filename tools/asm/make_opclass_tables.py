@@ -12,15 +12,21 @@ Classes: f64 = v_fma/fmac/mul/add_f64; trans = v_rcp/rsq/sqrt_f64; divh = v_div_
 TH_TEXT = "As profiles/r06_opclass_iso.md, for the thermal variant (`python tools/asm/isa.py thermal integrate <production flags of the thermal variants>`, `tools/asm/opclass.py /tmp/asm/thermal_integrate.s --from %d --md`)."
 
 
+PREFIX = sys.argv[1] if len(sys.argv) > 1 else "r06"       # (a later state of the tree is written under a name of its own: profiles/<prefix>_opclass_<model>.md)
+ONLY = sys.argv[2:]                                       # (models to regenerate; default both)
+
+
 def gen(model, title, flags, text):
+    if ONLY and model not in ONLY:
+        return
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm", "isa.py"), model, "integrate"] + flags, capture_output=True, text=True)
     res = [l for l in r.stdout.splitlines() if "load-store-opt" not in l][:6]
     asm = "/tmp/asm/%s_integrate.s" % model
     tics = [k for k, l in enumerate(open(asm), 1) if l.strip() == "; PLMARK tic"]
     first = tics[2]
     tab = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm", "opclass.py"), asm, "--from", str(first), "--md"], capture_output=True, text=True).stdout
-    out = os.path.join(ROOT, "profiles", "r06_opclass_%s.md" % model)
-    open(out, "w").write("# Opcode classes of `k_integrate<%s, 0>`: the step loop (static counts per marked region, r06)\n\n%s\n\n%s\n\n%s" % (title, text % first, "\n".join("    " + l for l in res), tab))
+    out = os.path.join(ROOT, "profiles", "%s_opclass_%s.md" % (PREFIX, model))
+    open(out, "w").write("# Opcode classes of `k_integrate<%s, 0>`: the step loop (static counts per marked region, %s)\n\n%s\n\n%s\n\n%s" % (title, PREFIX, text % first, "\n".join("    " + l for l in res), tab))
     print(out, "from line", first, [l.strip() for l in res[:6]])
 
 

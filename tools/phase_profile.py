@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-phase shader-cycle breakdown of k_integrate (profiling build libpetlion_hip_prof.so, -DPL_PHASE_TIMERS).
-usage (GPU box): python tools/phase_profile.py [n_cells]"""
+usage (GPU box): python tools/phase_profile.py [n_cells] [iso|thermal|sei|iso2] [--detail|--detail2|--detail3|--detail4] [--old-boundary] [--build-only]
+--detail4: the two stretches of the step loop no other timer covers (head of ida_step, loop control of cell_simulate).
+--old-boundary: the plain kernel with the separate step-boundary passes (-DPL_OLD_STEP_BOUNDARY), for before / after figures of the same source."""
 import os, sys, subprocess
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,11 +10,13 @@ sys.path.insert(0, ROOT)
 import pkgload
 pkg = pkgload.load()
 import __graft_entry__ as g
-detail = 1 if "--detail" in sys.argv else 2 if "--detail2" in sys.argv else 3 if "--detail3" in sys.argv else 0
+detail = 1 if "--detail" in sys.argv else 2 if "--detail2" in sys.argv else 3 if "--detail3" in sys.argv else 4 if "--detail4" in sys.argv else 0
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 which = args[1] if len(args) > 1 else "iso"
 variant = {"iso": 0, "thermal": 4, "sei": 3, "iso2": 13}[which]
-lib = g.build_hip(extra_flags=["-DPL_PHASE_TIMERS"] + (["-DPL_PHASE_DETAIL=%d" % detail] if detail else []), lib=os.path.join(ROOT, "petlion.jl_amd", "_exp", "libplh_prof_%s%s.so" % (which, "_d%d" % detail if detail else "")), variants=[variant])
+old = "--old-boundary" in sys.argv
+lib = g.build_hip(extra_flags=["-DPL_PHASE_TIMERS"] + (["-DPL_PHASE_DETAIL=%d" % detail] if detail else []) + (["-DPL_OLD_STEP_BOUNDARY"] if old else []),
+                  lib=os.path.join(ROOT, "petlion.jl_amd", "_exp", "libplh_prof_%s%s%s.so" % (which, "_d%d" % detail if detail else "", "_oldsb" if old else "")), variants=[variant])
 if "--build-only" in sys.argv:          # (here, without a GPU: the library travels to the GPU box with the snapshot)
     print(lib); sys.exit(0)
 import torch
@@ -35,6 +39,8 @@ if detail == 2:
     names = ["solve a: particle partial solutions", "solve b: fold into node rhs", "solve c: block sweeps", "solve d,e: border + node-local back-substitution", "solve f: particle update", "residual: node pass", "residual: particle rows", "TOTAL"]
 elif detail == 3:
     names = ["set_coeffs", "test_error", "complete_step", "get_solution", "SOC + save point", "check_stop", "previous point + rest", "TOTAL"]
+elif detail == 4:
+    names = ["ida_step head (to set_coeffs)", "loop control (output end to ida_step)", "-", "-", "-", "-", "-", "TOTAL"]
 elif detail:
     names = ["jac: node pass", "jac: particle rows", "factor: resolvents+collectors", "factor: node-local elimination", "factor: block sweep", "factor: control row+border", "-", "TOTAL"]
 cyc = ens.counters["cyc"].astype(np.float64)
@@ -45,8 +51,8 @@ for k, nm in enumerate(names):
     print("  %-50s %10.0f cyc  %5.1f%%" % (nm, cyc[:, k].mean(), 100 * cyc[:, k].mean() / tot))
 if detail == 2:
     print("  per solve:", ", ".join("%s %.0f" % (nm.split(":")[0], cyc[:, k].mean() / c["n_solve"].mean()) for k, nm in enumerate(names[:5])), "; per residual:", ", ".join("%.0f" % (cyc[:, k].mean() / c["n_res"].mean()) for k in (5, 6)))
-elif detail == 3:
-    print("  per step:", ", ".join("%s %.0f" % (nm, cyc[:, k].mean() / c["n_steps"].mean()) for k, nm in enumerate(names[:7])))
+elif detail in (3, 4):
+    print("  per step:", ", ".join("%s %.0f" % (nm, cyc[:, k].mean() / c["n_steps"].mean()) for k, nm in enumerate(names[:7]) if nm != "-"))
 elif detail:
     print("  per Jacobian refresh:", ", ".join("%s %.0f" % (nm, cyc[:, k].mean() / c["n_jac"].mean()) for k, nm in enumerate(names[:6])))
 else:
