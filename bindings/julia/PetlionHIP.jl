@@ -401,6 +401,107 @@ function lsq_multi(m::Model, ens, tq::Vector{Float64}, channels; interp_bc = :in
     (cost = cost, grad = grad, JtJ = JtJ, resid = res, status = status)
 end
 
+# ---- Levenberg-Marquardt fit per cell on the device (plh_lm_step; include/petlion_hip.h states what a step does) ----
+# plh_lm_opts; the defaults are PLH_LM_OPTS_DEFAULT
+struct LMOpts
+    lambda0::Cdouble
+    lambda_up::Cdouble
+    lambda_down::Cdouble
+    lambda_min::Cdouble
+    lambda_max::Cdouble
+    eta::Cdouble
+    ftol::Cdouble
+    xtol::Cdouble
+    gtol::Cdouble
+    diag_floor::Cdouble
+end
+LMOpts(; lambda0 = 1e-3, lambda_up = 3.0, lambda_down = 1 / 3, lambda_min = 1e-12, lambda_max = 1e12, eta = 1e-4, ftol = 1e-10, xtol = 1e-8, gtol = 1e-8, diag_floor = 1e-12) =
+    LMOpts(lambda0, lambda_up, lambda_down, lambda_min, lambda_max, eta, ftol, xtol, gtol, diag_floor)
+const LM_LINEAR, LM_LOG = Cint(0), Cint(1)
+const LM_FIRST, LM_STEP, LM_LAST = Cint(0), Cint(1), Cint(2)
+const LM_STATES = (:running, :conv_f, :conv_x, :conv_g, :maxit, :stalled, :failed_start)      # state + 1 indexes it
+
+"""
+    LMState(n, k)
+
+The per-cell state of a fit, owned by the caller and carried between `lm_step` calls: `θ_cur` k × n, `cost_cur` n, `grad_cur` k × n, `JtJ_cur` k × k × n, `λ`, `pred` n,
+`state`, `n_accept`, `n_reject` n (Cint).
+"""
+struct LMState
+    θ_cur::Matrix{Float64}
+    cost_cur::Vector{Float64}
+    grad_cur::Matrix{Float64}
+    JtJ_cur::Array{Float64, 3}
+    λ::Vector{Float64}
+    pred::Vector{Float64}
+    state::Vector{Cint}
+    n_accept::Vector{Cint}
+    n_reject::Vector{Cint}
+end
+LMState(n::Integer, k::Integer) = LMState(fill(NaN, k, n), fill(NaN, n), fill(NaN, k, n), fill(NaN, k, k, n), fill(NaN, n), fill(NaN, n), zeros(Cint, n), zeros(Cint, n), zeros(Cint, n))
+
+"""
+    lm_step(m, Θt, cols, transform, fit, st, phase; lo = nothing, hi = nothing, opts = LMOpts())
+
+One Levenberg-Marquardt iteration of every cell (`plh_lm_step`).  `Θt` is n_theta × n (one cell per column: the C layout), in: the point `fit = lsq(...)` belongs to, out:
+the next trial, or the cell's best point when it is done.  `cols` are 0-based θ columns in the order of the sens keys, `transform` `LM_LINEAR` / `LM_LOG` per key, `lo` / `hi`
+vectors of length k (shared) or k × n matrices (per cell), `nothing` = unbounded.  Returns the number of cells still running.
+"""
+function lm_step(m::Model, Θt::Matrix{Float64}, cols::Vector{Cint}, transform::Vector{Cint}, fit, st::LMState, phase::Cint; lo = nothing, hi = nothing, opts = LMOpts())
+    k, n = length(cols), size(Θt, 2)
+    per_cell = (lo !== nothing && ndims(lo) == 2) || (hi !== nothing && ndims(hi) == 2)
+    full(b) = b === nothing ? nothing : (per_cell && ndims(b) == 1 ? repeat(b, 1, n) : Array{Float64}(b))
+    l, h = full(lo), full(hi)
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    n_running = Ref{Cint}(0)
+    GC.@preserve l h begin
+        check(ccall((:plh_lm_step, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint},
+                     Ref{LMOpts}, Cint, Ref{Cint}, Cint, Ptr{Cvoid}),
+                    m.h, n, size(Θt, 1), Θt, k, cols, transform, p(l), p(h), per_cell ? 1 : 0,
+                    fit.cost, fit.grad, fit.JtJ, fit.status,
+                    st.θ_cur, st.cost_cur, st.grad_cur, st.JtJ_cur, st.λ, st.pred, st.state, st.n_accept, st.n_reject,
+                    Ref(opts), phase, n_running, PLH_HOST, C_NULL),
+              "plh_lm_step")
+    end
+    Int(n_running[])
+end
+
+"""
+    fit_ensemble(m, p, Θ0, protocol, keys, tq, channels; bounds = Dict(), transform = Dict(), max_iter = 30, SOC, max_pts, opts = LMOpts())
+
+Fit `keys` of every cell (row of `Θ0`, n × n_theta) to measured curves: per iteration one `simulate_ensemble_sens`, one `lsq_multi` and one `lm_step`.  `channels` as
+`lsq_multi` takes them (`[(:V, y, w), (:I, y, w)]`); `bounds = Dict(key => (lo, hi))`, `transform = Dict(key => :log)`.  At most `max_iter + 1` integrations.  Cells that are
+done keep being integrated at their best point.  Returns `(θ, cost, grad, JtJ, state, λ, n_accept, n_reject, n_iter)` with `θ` n × n_theta.
+"""
+function fit_ensemble(m::Model, p, Θ0::Matrix{Float64}, protocol, keys::Vector{Symbol}, tq::Vector{Float64}, channels;
+                      bounds = Dict(), transform = Dict(), max_iter = 30, SOC = p.opts.SOC, max_pts = 2048, opts = LMOpts())
+    1 <= length(keys) <= 8 || error("fit_ensemble fits 1 .. 8 keys per call")
+    n, k = size(Θ0, 1), length(keys)
+    cols = Cint[key_index(m, key) - 1 for key in keys]
+    tf = Cint[get(transform, key, :linear) == :log ? LM_LOG : LM_LINEAR for key in keys]
+    lo = Float64[get(bounds, key, (-Inf, Inf))[1] for key in keys]
+    hi = Float64[get(bounds, key, (-Inf, Inf))[2] for key in keys]
+    outputs = Tuple(c[1] for c in channels)
+    Θt = permutedims(Θ0)                                            # n_theta × n: a copy, the caller's Θ0 is not modified
+    st = LMState(n, k)
+    n_iter = 0
+    iteration(phase) = begin
+        ens = simulate_ensemble_sens(m, p, permutedims(Θt), protocol, keys; SOC = SOC, max_pts = max_pts, outputs = outputs)
+        n_iter += 1
+        lm_step(m, Θt, cols, tf, lsq_multi(m, ens, tq, channels), st, phase; lo = lo, hi = hi, opts = opts)
+    end
+    running = iteration(LM_FIRST)
+    for _ in 2:max_iter
+        running == 0 && break
+        running = iteration(LM_STEP)
+    end
+    running == 0 || iteration(LM_LAST)
+    (θ = permutedims(Θt), cost = st.cost_cur, grad = st.grad_cur, JtJ = st.JtJ_cur, state = st.state, λ = st.λ, n_accept = st.n_accept, n_reject = st.n_reject, n_iter = n_iter)
+end
+
 # ---- seam 1: the five generated functions of p.funcs (src/structures.jl:315-334) as single-cell evaluators ----
 function residual!(res::Vector{Float64}, m::Model, Y, YP, θ; mode = :I, value = 0.0)
     check(ccall((:plh_residual, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cvoid}),

@@ -459,6 +459,79 @@ int plh_lsq_multi(plh_model_t m, int n_cells, int n_runs, int max_pts, const dou
                   double* cost /* [n_cells] */, double* grad /* [n_cells][n_sens] */, double* JtJ /* [n_cells][n_sens][n_sens], full symmetric */,
                   int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
 
+/* ---- one Levenberg-Marquardt iteration per cell on the device: judges the trial that was just integrated, updates the damping, tests convergence, solves the damped,
+ * scaled, box-bounded normal equations and writes the next trial into the cell's theta row.  A fit is: integrate with sensitivities, plh_lsq / plh_lsq_multi, plh_lm_step
+ * (PLH_LM_FIRST); then integrate, lsq, plh_lm_step (PLH_LM_STEP) until *n_running == 0 or the budget is spent; then integrate, lsq, plh_lm_step (PLH_LM_LAST).  One
+ * sensitivity integration per iteration: an accepted trial carries its own grad / JtJ.
+ *
+ * Arguments.  k = n_keys (1 .. PLH_LSQ_MAX_SENS).  cols[k] (theta columns, in the order of the sens keys) and transform[k] (PLH_LM_LINEAR: u = theta, PLH_LM_LOG: u = ln theta)
+ * are HOST memory for every ptr_kind, and so are shared bounds; every other array follows ptr_kind (PLH_HOST blocks; PLH_DEVICE is asynchronous on `stream`).
+ *   theta[n][n_theta]   in: the point that was just integrated; out: the next trial, or the cell's best point when the cell is done.  Only columns in cols are ever written.
+ *   lo, hi              bounds in theta units: [k] in HOST memory (bounds_per_cell = 0) or [n][k] following ptr_kind (1); a NULL lo is -inf, a NULL hi is +inf
+ *   cost[n], grad[n][k], JtJ[n][k][k], status[n]     the fit of the point in theta, as plh_lsq_multi wrote it (status may be NULL = 0 everywhere).  Only JtJ's upper triangle
+ *                                                    (row <= column) is used; JtJ_cur receives the full copy.
+ *   theta_cur[n][k], cost_cur[n], grad_cur[n][k], JtJ_cur[n][k][k], lambda[n], pred[n], state[n], n_accept[n], n_reject[n]
+ *                       the per-cell state, owned by the caller and carried between the calls of one fit; PLH_LM_FIRST initialises it
+ *   n_running           one int: the number of cells with state == PLH_LM_RUNNING after the call
+ *   o                   NULL = PLH_LM_OPTS_DEFAULT
+ *
+ * Per cell ("finite": neither NaN nor +-inf; "the fit": cost, grad and the upper triangle of JtJ; theta_i: the entry of column cols[i]):
+ *  Done cells.  Phase STEP / LAST with state != PLH_LM_RUNNING: nothing of the cell is written -- its theta row and every state array keep their bits.  Phase FIRST ignores
+ *    the incoming state.
+ *  Phase FIRST.  The start is bad if status != 0, or the fit is not finite, or for some key theta_i is not finite, or not (lo_i <= theta_i <= hi_i) (so a per-cell lo_i > hi_i
+ *    or a NaN bound is a bad start), or theta_i <= 0 under PLH_LM_LOG.  A bad start: state = PLH_LM_FAILED_START, and nothing else of the cell is written.  Otherwise
+ *    cur <- the incoming point (theta_cur, cost_cur, grad_cur, JtJ_cur), lambda = lambda0, pred = 0, n_accept = n_reject = 0, state = PLH_LM_RUNNING; go to Propose.
+ *  Phase STEP / LAST, judging the trial.  ok = (status == 0 and the fit is finite); actual = cost_cur - cost; accept iff ok and actual >= eta * pred.
+ *    Accept: cur <- the trial (theta_cur, cost_cur, grad_cur, JtJ_cur), lambda = max(lambda * lambda_down, lambda_min), n_accept++; if actual <= ftol * (the old cost_cur):
+ *            state = PLH_LM_CONV_F.
+ *    Reject: lambda = lambda * lambda_up, n_reject++, theta_i <- theta_cur_i; if lambda > lambda_max: state = PLH_LM_STALLED.
+ *    Phase LAST: a cell still RUNNING after judging gets state = PLH_LM_MAXIT, theta_i <- theta_cur_i, and nothing is proposed.
+ *  Propose (FIRST and STEP, cells still RUNNING), with g, H, theta from the cur arrays:
+ *    Scaling:     s_i = theta_i for a LOG key, 1 for a LINEAR key; gs_i = s_i g_i; Hs_ij = (s_i s_j) H_ij.
+ *                 A gs_i or Hs_ij that is not finite (the scaling overflowed): state = PLH_LM_STALLED, theta stays at cur.
+ *    Active set:  key i is held if (theta_i <= lo_i and gs_i > 0) or (theta_i >= hi_i and gs_i < 0); the others are free.
+ *    Gradient test (MINPACK's cosine): no free key, or cost_cur == 0, or |gs_i| <= gtol * sqrt(Hs_ii * 2 cost_cur) for every free key (a free key with Hs_ii == 0 has
+ *                 gs_i == 0 and passes): state = PLH_LM_CONV_G, theta stays at cur.
+ *    Damping:     D_i = max(Hs_ii, diag_floor * max_j Hs_jj), the maximum over all k keys.
+ *    Solve, at most PLH_LM_MAX_TRIES tries: A = Hs_ff + lambda diag(D_f) over the free keys; Cholesky A = L L^T, row by row (a pivot that is <= 0 or not finite fails);
+ *                 d_f = -A^-1 gs_f, d = 0 for held keys; trial_i = theta_i + d_i (LINEAR) or theta_i exp(d_i) (LOG: u + d transformed back), clamped to [lo_i, hi_i];
+ *                 for a key the clamp moved, d_i = trial_i - theta_i (LINEAR) or ln(trial_i / theta_i) (LOG): the step actually taken in u;
+ *                 pred = -(gs.d + 1/2 d.Hs d).
+ *                 A Cholesky failure, a trial that is not finite, or not (pred > 0): lambda = lambda * lambda_up; if lambda > lambda_max: state = PLH_LM_STALLED, theta stays
+ *                 at cur; else try again.  After PLH_LM_MAX_TRIES failed tries the cell is PLH_LM_STALLED as well.
+ *    Step test:   m_i = |d_i| (LOG) or |d_i| / max(|theta_i|, DBL_MIN) (LINEAR); if m_i <= xtol for every key: state = PLH_LM_CONV_X, theta stays at cur (the step is not taken).
+ *    Otherwise    theta_i <- trial_i, and pred is stored.
+ * Nothing in the arithmetic depends on the launch shape or the pointer kind: the bits of every output are the same for PLH_HOST and PLH_DEVICE.
+ * PLH_E_ARG, nothing written: n_cells < 1; n_keys outside 1 .. PLH_LSQ_MAX_SENS; n_theta < 1; a column outside [0, n_theta) or given twice; an unknown transform or phase;
+ * bounds_per_cell not 0 / 1; a NULL among theta, cols, transform, cost, grad, JtJ, the state arrays and n_running; lambda_up <= 1, lambda_down outside (0, 1), lambda0 <= 0,
+ * lambda_min < 0, lambda_max < lambda_min, eta < 0, a negative ftol / xtol / gtol / diag_floor (or a NaN in any option); shared bounds with lo_i > hi_i or a NaN. */
+#define PLH_LM_LINEAR 0
+#define PLH_LM_LOG 1
+#define PLH_LM_FIRST 0
+#define PLH_LM_STEP 1
+#define PLH_LM_LAST 2
+#define PLH_LM_RUNNING 0
+#define PLH_LM_CONV_F 1        /* the accepted step lowered the cost by <= ftol * cost */
+#define PLH_LM_CONV_X 2        /* the proposed step is <= xtol in every key */
+#define PLH_LM_CONV_G 3        /* the projected gradient test passed */
+#define PLH_LM_MAXIT 4         /* still running at PLH_LM_LAST */
+#define PLH_LM_STALLED 5       /* lambda passed lambda_max, or PLH_LM_MAX_TRIES failed solves */
+#define PLH_LM_FAILED_START 6  /* the starting point cannot be used */
+#define PLH_LM_MAX_TRIES 16
+typedef struct {
+  double lambda0, lambda_up, lambda_down, lambda_min, lambda_max;
+  double eta, ftol, xtol, gtol, diag_floor;
+} plh_lm_opts;
+#define PLH_LM_OPTS_DEFAULT { 1e-3, 3.0, 1.0 / 3.0, 1e-12, 1e12, 1e-4, 1e-10, 1e-8, 1e-8, 1e-12 }
+int plh_lm_step(plh_model_t m, int n_cells, int n_theta, double* theta /* [n_cells][n_theta] */,
+                int n_keys, const int* cols, const int* transform, const double* lo, const double* hi, int bounds_per_cell,
+                const double* cost, const double* grad, const double* JtJ, const int* status,
+                double* theta_cur, double* cost_cur, double* grad_cur, double* JtJ_cur, double* lambda, double* pred,
+                int* state, int* n_accept, int* n_reject,
+                const plh_lm_opts* o, int phase, int* n_running, int ptr_kind, void* stream);
+/* sizeof / offsetof of plh_lm_opts, in plh_abi_layout's format (sizeof, number of fields, the offsets) */
+int plh_lm_abi_layout(int* out, int cap);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

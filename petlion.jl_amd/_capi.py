@@ -23,6 +23,11 @@ VAL_CONST, VAL_HOLD, VAL_REST, VAL_TABLE, VAL_EXPR = 0, 1, 2, 3, 4
 CHEM_LCO, CHEM_NMC, CHEM_LGM50 = 0, 1, 2
 LSQ_MAX_SENS = 8
 LSQ_MAX_CHANNELS = 3
+LM_LINEAR, LM_LOG = 0, 1
+LM_FIRST, LM_STEP, LM_LAST = 0, 1, 2
+LM_RUNNING, LM_CONV_F, LM_CONV_X, LM_CONV_G, LM_MAXIT, LM_STALLED, LM_FAILED_START = 0, 1, 2, 3, 4, 5, 6
+LM_MAX_TRIES = 16
+LM_STATE_NAMES = ["RUNNING", "CONV_F", "CONV_X", "CONV_G", "MAXIT", "STALLED", "FAILED_START"]
 FLAG_RUNNING, ERR_INIT, ERR_STALL, ERR_MAXITERS, ERR_OUTPUT_FULL = -1, -11, -12, -13, -14
 
 BOUND_FIELDS = ["V_max", "V_min", "SOC_max", "SOC_min", "T_max", "c_s_n_max", "I_max", "I_min", "eta_plating_min",
@@ -81,6 +86,20 @@ class LsqChannel(C.Structure):             # plh_lsq_channel
     _fields_ = [("curve", C.c_void_p), ("dcurve", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p), ("resid", C.c_void_p)]
 
 
+LM_OPT_FIELDS = ["lambda0", "lambda_up", "lambda_down", "lambda_min", "lambda_max", "eta", "ftol", "xtol", "gtol", "diag_floor"]
+LM_OPT_DEFAULTS = dict(zip(LM_OPT_FIELDS, (1e-3, 3.0, 1.0 / 3.0, 1e-12, 1e12, 1e-4, 1e-10, 1e-8, 1e-8, 1e-12)))      # PLH_LM_OPTS_DEFAULT
+
+
+class LMOpts(C.Structure):                 # plh_lm_opts
+    _fields_ = [(f, C.c_double) for f in LM_OPT_FIELDS]
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(LM_OPT_FIELDS)
+        if unknown:
+            raise ValueError("unknown Levenberg-Marquardt option(s) %s (there are: %s)" % (sorted(unknown), ", ".join(LM_OPT_FIELDS)))
+        super().__init__(**{**LM_OPT_DEFAULTS, **kw})
+
+
 RUN_INFO_DTYPE = np.dtype([("flag", np.int32), ("iterations", np.int32), ("t_end", np.float64), ("V", np.float64),
                            ("I", np.float64), ("SOC", np.float64), ("T_avg", np.float64)], align=True)
 COUNTERS_DTYPE = np.dtype([(f, np.int64) for f in COUNTER_FIELDS] + [("cyc", np.int64, (8,))], align=True)
@@ -89,7 +108,7 @@ assert RUN_INFO_DTYPE.itemsize == C.sizeof(RunInfo) and COUNTERS_DTYPE.itemsize 
 EXPORTS = ["plh_model_create", "plh_model_destroy", "plh_register_grid_library", "plh_n_states", "plh_n_diff", "plh_n_theta", "plh_theta_key",
            "plh_theta_default", "plh_lds_bytes", "plh_n_sections", "plh_section", "plh_jac_pattern", "plh_jac_alg_pattern", "plh_last_error", "plh_build_info", "plh_device_count", "plh_abi_layout",
            "plh_initial_guess", "plh_residual", "plh_jacobian", "plh_linear_solve", "plh_linear_solve_refined", "plh_residual_diff", "plh_residual_alg",
-           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
+           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_lm_step", "plh_lm_abi_layout", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
            "plh_comm_unique_id", "plh_comm_create", "plh_comm_destroy", "plh_comm_rank", "plh_comm_size", "plh_ensemble_run"]
 
 
@@ -157,6 +176,8 @@ def load(path=None):
     lib.plh_resample.argtypes = [vp, i, i, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, i, vp]
     lib.plh_lsq.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, vp]
     lib.plh_lsq_multi.argtypes = [vp, i, i, i, vp, vp, vp, i, C.POINTER(LsqChannel), i, i, vp, i, i, vp, vp, vp, vp, i, vp]
+    lib.plh_lm_step.argtypes = [vp, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LMOpts), i, vp, i, vp]
+    lib.plh_lm_abi_layout.argtypes = [vp, i]
     _cache[path] = lib
     return lib
 

@@ -1184,6 +1184,136 @@ def simulate_ensemble(p, Theta, protocol, *, SOC=None, opts=None, device=False, 
     return EnsembleSolution(p, bufs, names, sel, sel_ind)
 
 
+class EnsembleFitResult:
+    """fit_ensemble's result.  theta [n, n_theta]: every cell's best point; cost [n], grad [n, k], JtJ [n, k, k]: the fit at that point (NaN for a cell whose start could not
+    be used); state [n] (cap.LM_*: CONV_F / CONV_X / CONV_G / MAXIT / STALLED / FAILED_START, names in cap.LM_STATE_NAMES), lam [n], n_accept [n], n_reject [n]; n_iter: the
+    number of integrations; keys; history: None, or per iteration a dict of host copies (phase, theta_before / theta_after, cost, grad, JtJ, status, before / after: the
+    per-cell state arrays, n_running)."""
+
+    def __init__(self, keys):
+        self.keys = list(keys)
+        self.theta = self.cost = self.grad = self.JtJ = self.state = self.lam = self.n_accept = self.n_reject = self.history = None
+        self.n_iter = 0
+
+
+LM_STATE_ARRAYS = ("theta_cur", "cost_cur", "grad_cur", "JtJ_cur", "lam", "pred", "state", "n_accept", "n_reject")
+
+
+def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data=None, I_weights=None, T_avg_data=None, T_avg_weights=None, *, bounds=None, transform=None,
+                 max_iter=30, check_every=1, SOC=None, opts=None, lm=None, device=False, stream=None, max_points=None, interp_bc="interpolate", history=False):
+    """Levenberg-Marquardt fit of every cell's `keys` to measured curves, the loop on the device: per iteration one sensitivity integration (simulate_ensemble(sens=keys)),
+    ens.lsq(t, ...) and one plh_lm_step (csrc/plh_lm.h; include/petlion_hip.h states what a step does), which judges the trial, updates the damping, tests convergence, solves
+    the damped, scaled, bounded normal equations and writes the next trial into Theta -- all in HBM with device=True, where the 4-byte read of the number of running cells every
+    `check_every` iterations is the loop's only synchronisation.
+    Theta0 [n, n_theta] (not modified); protocol, SOC, opts, max_points, device, stream as simulate_ensemble; t and the data / weights of the channels as ens.lsq (the channels
+    given data are the ones differentiated).  bounds = {key: (lo, hi)}, scalars or [n_cells] arrays, None = unbounded on that side; transform = {key: "log" | "linear"} (default
+    linear; log: the step is taken in ln theta, the parameter must be positive); lm = {option: value} over cap.LM_OPT_DEFAULTS.  At most max_iter + 1 integrations: the first
+    point, up to max_iter - 1 steps, and one last judgement.  Cells that are done keep being integrated at their best point (the ensemble is not compacted).
+    Returns an EnsembleFitResult."""
+    keys = list(keys)
+    if len(keys) < 1 or len(keys) > cap.LSQ_MAX_SENS:
+        raise ValueError("fit_ensemble fits 1 .. %d keys per call (%d given)" % (cap.LSQ_MAX_SENS, len(keys)))
+    for kname in keys:
+        if kname not in p.θ_keys:
+            raise ValueError("fit_ensemble: %r is not a parameter of this model's theta" % (kname,))
+    if len(set(keys)) != len(keys):
+        raise ValueError("fit_ensemble: a key given twice")
+    given = [c for c, d in (("V", V_data), ("I", I_data), ("T_avg", T_avg_data)) if d is not None]
+    if not given:
+        raise ValueError("fit_ensemble needs the data of at least one channel: V_data, I_data or T_avg_data")
+    for what, dct in (("bounds", bounds), ("transform", transform)):
+        for kname in (dct or {}):
+            if kname not in keys:
+                raise ValueError("fit_ensemble: %s names %r, which is not among the keys" % (what, kname))
+    tf = np.zeros(len(keys), np.int32)
+    for kname, v in (transform or {}).items():
+        if v not in ("log", "linear"):
+            raise ValueError("fit_ensemble: transform of %r must be 'log' or 'linear', not %r" % (kname, v))
+        tf[keys.index(kname)] = cap.LM_LOG if v == "log" else cap.LM_LINEAR
+    if max_iter < 1 or check_every < 1:
+        raise ValueError("fit_ensemble: max_iter and check_every must be >= 1")
+    lmo = cap.LMOpts(**(lm or {}))
+    n, nth, k = Theta0.shape[0], Theta0.shape[1], len(keys)
+    cols = np.ascontiguousarray([p.θ_keys.index(kname) for kname in keys], dtype=np.int32)
+    if device:
+        import torch
+        dev = Theta0.device
+        Theta = Theta0.to(dtype=torch.float64).contiguous().clone()
+        mk = lambda shape, dt=torch.float64, fill=float("nan"): torch.full(shape, fill, dtype=dt, device=dev)
+        mki = lambda shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+
+        def host(a):                                                     # (the launch stream need not be torch's current one: it is waited for, then the copy is plain)
+            cap.check(p._lib, p._lib.plh_synchronize(p._h, stream), "plh_synchronize")
+            return a.cpu().numpy().copy()
+        kind = cap.PLH_DEVICE
+    else:
+        Theta = np.array(Theta0, dtype=np.float64, order="C", copy=True)
+        mk = lambda shape, dt=np.float64, fill=np.nan: np.full(shape, fill, dt)
+        mki = lambda shape: np.zeros(shape, np.int32)
+        host = lambda a: np.array(a, copy=True)
+        kind = cap.PLH_HOST
+    # bounds: [k] on the host when every one is a scalar, else [n, k] where Theta lives
+    blo, bhi = np.full(k, -np.inf), np.full(k, np.inf)
+    per_cell = any(b is not None and np.ndim(b.cpu() if hasattr(b, "cpu") else b) > 0 for pair in (bounds or {}).values() for b in pair)
+    if per_cell:
+        blo, bhi = np.full((n, k), -np.inf), np.full((n, k), np.inf)
+    for kname, pair in (bounds or {}).items():
+        if len(pair) != 2:
+            raise ValueError("fit_ensemble: bounds[%r] must be (lo, hi)" % (kname,))
+        for dst, b in zip((blo, bhi), pair):
+            if b is None:
+                continue
+            b = np.asarray(b.cpu() if hasattr(b, "cpu") else b, dtype=np.float64)
+            if b.ndim and b.shape != (n,):
+                raise ValueError("fit_ensemble: a bound of %r must be a scalar or [n_cells]" % (kname,))
+            dst[..., keys.index(kname)] = b
+    if per_cell and device:
+        lo_a, hi_a = torch.as_tensor(blo).to(dev), torch.as_tensor(bhi).to(dev)
+    else:
+        lo_a, hi_a = np.ascontiguousarray(blo), np.ascontiguousarray(bhi)
+    st = dict(theta_cur=mk((n, k)), cost_cur=mk((n,)), grad_cur=mk((n, k)), JtJ_cur=mk((n, k, k)), lam=mk((n,)), pred=mk((n,)), state=mki((n,)), n_accept=mki((n,)), n_reject=mki((n,)))
+    n_running = mki((1,))
+    ext = None
+    if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+        ext = torch.cuda.ExternalStream(int(stream), device=dev)         # (made on torch's current stream, used on the launch stream: as in _integrate)
+        ext.wait_stream(torch.cuda.current_stream(dev))
+        for v in [Theta, n_running, lo_a, hi_a] + list(st.values()):
+            if hasattr(v, "record_stream"):
+                v.record_stream(ext)
+    res = EnsembleFitResult(keys)
+    res.history = [] if history else None
+    lib, h = p._lib, p._h
+
+    def iteration(phase):
+        ens = simulate_ensemble(p, Theta, protocol, SOC=SOC, opts=opts, device=device, stream=stream, max_points=max_points, YP=False, sens=keys, sens_outputs=tuple(given))
+        fit = ens.lsq(t, V_data, weights, interp_bc=interp_bc, I_data=I_data, I_weights=I_weights, T_avg_data=T_avg_data, T_avg_weights=T_avg_weights)
+        if history:
+            rec = dict(phase=phase, theta_before=host(Theta), cost=host(fit.cost), grad=host(fit.grad), JtJ=host(fit.JtJ), status=host(fit.status), before={a: host(v) for a, v in st.items()})
+        cap.check(lib, lib.plh_lm_step(h, n, nth, cap.ptr(Theta), k, cols.ctypes.data, tf.ctypes.data, cap.ptr(lo_a), cap.ptr(hi_a), 1 if per_cell else 0,
+                                       cap.ptr(fit.cost), cap.ptr(fit.grad), cap.ptr(fit.JtJ), cap.ptr(fit.status),
+                                       cap.ptr(st["theta_cur"]), cap.ptr(st["cost_cur"]), cap.ptr(st["grad_cur"]), cap.ptr(st["JtJ_cur"]), cap.ptr(st["lam"]), cap.ptr(st["pred"]),
+                                       cap.ptr(st["state"]), cap.ptr(st["n_accept"]), cap.ptr(st["n_reject"]), C.byref(lmo), phase, cap.ptr(n_running), kind, stream), "plh_lm_step")
+        res.n_iter += 1
+        if history:
+            rec.update(theta_after=host(Theta), after={a: host(v) for a, v in st.items()}, n_running=int(host(n_running)[0]))
+            res.history.append(rec)
+
+    read_running = lambda: int(host(n_running)[0])                       # (device=True: the loop's only synchronisation)
+    iteration(cap.LM_FIRST)
+    running = read_running() if check_every == 1 else 1
+    for it in range(1, max_iter):
+        if running == 0:
+            break
+        iteration(cap.LM_STEP)
+        if it % check_every == 0:
+            running = read_running()
+    if running != 0 and read_running() != 0:
+        iteration(cap.LM_LAST)
+    res.theta, res.cost, res.grad, res.JtJ = Theta, st["cost_cur"], st["grad_cur"], st["JtJ_cur"]
+    res.state, res.lam, res.n_accept, res.n_reject = st["state"], st["lam"], st["n_accept"], st["n_reject"]
+    return res
+
+
 def theta_matrix(p, n_cells, overrides=None):
     """[n_cells, n_theta] matrix of the model's current θ, with per-cell overrides {key: array[n_cells]}."""
     Th = np.tile(p.theta_vector(), (n_cells, 1))

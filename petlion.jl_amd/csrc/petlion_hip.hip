@@ -36,6 +36,7 @@
 
 #include "plh_resample.h"
 #include "plh_lsq.h"
+#include "plh_lm.h"
 
 using namespace pl;
 
@@ -187,6 +188,7 @@ struct StreamCtx {
   Uploaded<double> tdiscon, tstops;                         // opts.tdiscon / opts.tstops, sorted
   Uploaded<int> sel;                                        // packed entry -> state index of plh_outputs.sel (Y_sel); allocated at N ints, the longest selection there is
   DevBuf resample;                                          // plh_resample: elimination factors, query locations and slopes of one chunk of cells (plh_resample.h, plrs::Work)
+  Uploaded<double> lm_bounds;                               // plh_lm_step: shared bounds, lo[n_keys] then hi[n_keys] (remembered: the same for every iteration of a fit)
   Uploaded<double> resample_tq;                             // plh_resample: the query times (remembered: the fields of one ensemble are resampled on the same grid, one call each)
   hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
   std::vector<hipEvent_t> ret_ev;                           // one event per output array of a synchronous host call (host_return): grown on demand, kept
@@ -1348,6 +1350,72 @@ int plh_lsq_multi(plh_model_t m, int n, int n_runs, int max_pts, const double* t
   s.back(cost, A.cost, (size_t)n); s.back(grad, A.grad, n * ns); s.back(JtJ, A.JtJ, n * ns * ns);
   for (int c = 0; c < n_ch; c++) s.back(ch[c].resid, A.ch[c].resid, (size_t)n * n_q);
   s.back(status, a.status, (size_t)n);
+  CHECK_STAGE(s);
+  return 0;
+}
+
+// ---- plh_lm_step: one Levenberg-Marquardt iteration per cell (kernels: plh_lm.h).  cols, transform and shared bounds are host memory and travel in the kernel argument;
+// a PLH_HOST call stages every array whole, both ways: a cell the kernel does not write gets its own bits back ----
+int plh_lm_abi_layout(int* out, int cap) {
+  const int v[] = {(int)sizeof(plh_lm_opts), 10, (int)offsetof(plh_lm_opts, lambda0), (int)offsetof(plh_lm_opts, lambda_up), (int)offsetof(plh_lm_opts, lambda_down),
+                   (int)offsetof(plh_lm_opts, lambda_min), (int)offsetof(plh_lm_opts, lambda_max), (int)offsetof(plh_lm_opts, eta), (int)offsetof(plh_lm_opts, ftol),
+                   (int)offsetof(plh_lm_opts, xtol), (int)offsetof(plh_lm_opts, gtol), (int)offsetof(plh_lm_opts, diag_floor)};
+  const int nv = (int)(sizeof(v) / sizeof(v[0]));
+  for (int k = 0; k < nv && k < cap; k++) if (out) out[k] = v[k];
+  return nv;
+}
+int plh_lm_step(plh_model_t m, int n, int n_theta, double* theta, int n_keys, const int* cols, const int* transform, const double* lo, const double* hi, int bounds_per_cell,
+                const double* cost, const double* grad, const double* JtJ, const int* status, double* theta_cur, double* cost_cur, double* grad_cur, double* JtJ_cur,
+                double* lambda, double* pred, int* state, int* n_accept, int* n_reject, const plh_lm_opts* opts, int phase, int* n_running, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1 || n_theta < 1) return fail(PLH_E_ARG, "plh_lm_step: n_cells and n_theta must be >= 1");
+  if (n_keys < 1 || n_keys > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_lm_step: n_keys must be 1 .. PLH_LSQ_MAX_SENS (8)");
+  if (phase != PLH_LM_FIRST && phase != PLH_LM_STEP && phase != PLH_LM_LAST) return fail(PLH_E_ARG, "plh_lm_step: phase must be PLH_LM_FIRST, PLH_LM_STEP or PLH_LM_LAST");
+  if (bounds_per_cell != 0 && bounds_per_cell != 1) return fail(PLH_E_ARG, "plh_lm_step: bounds_per_cell must be 0 or 1");
+  if (!theta || !cols || !transform || !cost || !grad || !JtJ || !theta_cur || !cost_cur || !grad_cur || !JtJ_cur || !lambda || !pred || !state || !n_accept || !n_reject || !n_running)
+    return fail(PLH_E_ARG, "plh_lm_step: null array (only lo, hi, status and the options may be NULL)");
+  const plh_lm_opts dflt = PLH_LM_OPTS_DEFAULT;
+  const plh_lm_opts o = opts ? *opts : dflt;
+  if (!(o.lambda_up > 1.0) || !(o.lambda_down > 0.0 && o.lambda_down < 1.0) || !(o.lambda0 > 0.0) || !(o.lambda_min >= 0.0) || !(o.lambda_max >= o.lambda_min) || !(o.eta >= 0.0) ||
+      !(o.ftol >= 0.0) || !(o.xtol >= 0.0) || !(o.gtol >= 0.0) || !(o.diag_floor >= 0.0))
+    return fail(PLH_E_ARG, "plh_lm_step: options (lambda_up > 1, 0 < lambda_down < 1, lambda0 > 0, 0 <= lambda_min <= lambda_max, eta and the tolerances >= 0)");
+  pllm::Args A;
+  A.logmask = 0;
+  std::vector<double> shared(2 * (size_t)n_keys);                    // lo, then hi
+  for (int i = 0; i < pllm::NK; i++) A.cols[i] = 0;
+  for (int i = 0; i < n_keys; i++) {
+    if (cols[i] < 0 || cols[i] >= n_theta) return fail(PLH_E_ARG, "plh_lm_step: a column outside [0, n_theta)");
+    for (int j = 0; j < i; j++) if (cols[j] == cols[i]) return fail(PLH_E_ARG, "plh_lm_step: a column given twice");
+    if (transform[i] != PLH_LM_LINEAR && transform[i] != PLH_LM_LOG) return fail(PLH_E_ARG, "plh_lm_step: transform must be PLH_LM_LINEAR or PLH_LM_LOG");
+    A.cols[i] = cols[i];
+    if (transform[i] == PLH_LM_LOG) A.logmask |= 1u << i;
+    if (!bounds_per_cell) {
+      shared[i] = lo ? lo[i] : -HUGE_VAL; shared[n_keys + i] = hi ? hi[i] : HUGE_VAL;
+      if (!(shared[i] <= shared[n_keys + i])) return fail(PLH_E_ARG, "plh_lm_step: shared bounds with lo > hi (or a NaN)");
+    }
+  }
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  const size_t nn = (size_t)n, nk = nn * n_keys, nkk = nk * n_keys, nth = nn * n_theta;
+  A.n_cells = n; A.n_theta = n_theta; A.n_keys = n_keys; A.bstride = bounds_per_cell ? n_keys : 0; A.phase = phase; A.o = o;
+  A.theta = s.buf(theta, nth, true);
+  A.lo = bounds_per_cell ? s.in(lo, nk) : nullptr; A.hi = bounds_per_cell ? s.in(hi, nk) : nullptr;
+  if (!bounds_per_cell) {
+    const double* d_shared = nullptr;
+    if (int rc = s.cx->lm_bounds.get(s.cx->st, shared, &d_shared)) return rc;
+    A.lo = d_shared; A.hi = d_shared + n_keys;
+  }
+  A.cost = s.in(cost, nn); A.grad = s.in(grad, nk); A.JtJ = s.in(JtJ, nkk); A.status = s.in(status, nn);
+  A.theta_cur = s.buf(theta_cur, nk, true); A.cost_cur = s.buf(cost_cur, nn, true); A.grad_cur = s.buf(grad_cur, nk, true); A.JtJ_cur = s.buf(JtJ_cur, nkk, true);
+  A.lambda = s.buf(lambda, nn, true); A.pred = s.buf(pred, nn, true);
+  A.state = s.buf(state, nn, true); A.n_accept = s.buf(n_accept, nn, true); A.n_reject = s.buf(n_reject, nn, true);
+  int* d_count = s.buf(n_running, 1, false);
+  CHECK_STAGE(s);
+  pllm::launch(s.st, A, d_count);
+  FINISH(s);
+  s.back(theta, A.theta, nth); s.back(theta_cur, A.theta_cur, nk); s.back(cost_cur, A.cost_cur, nn); s.back(grad_cur, A.grad_cur, nk); s.back(JtJ_cur, A.JtJ_cur, nkk);
+  s.back(lambda, A.lambda, nn); s.back(pred, A.pred, nn); s.back(state, A.state, nn); s.back(n_accept, A.n_accept, nn); s.back(n_reject, A.n_reject, nn);
+  s.back(n_running, d_count, 1);
   CHECK_STAGE(s);
   return 0;
 }
