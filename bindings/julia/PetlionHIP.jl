@@ -502,6 +502,46 @@ function fit_ensemble(m::Model, p, Θ0::Matrix{Float64}, protocol, keys::Vector{
     (θ = permutedims(Θt), cost = st.cost_cur, grad = st.grad_cur, JtJ = st.JtJ_cur, state = st.state, λ = st.λ, n_accept = st.n_accept, n_reject = st.n_reject, n_iter = n_iter)
 end
 
+# ---- parameters shared by groups of consecutive cells (plh_lsq_group, plh_group_scatter; include/petlion_hip.h states the definition) ----
+"""
+    lsq_group(m, group_off, fit)
+
+The fits of the members of every group summed into one fit per group (`plh_lsq_group`): `group_off` are the n_groups + 1 ascending 0-based offsets (group g owns the cells
+`group_off[g] .. group_off[g + 1] - 1`, 0-based), `fit` what `lsq` / `lsq_multi` returned (cost n, grad k × n, JtJ k × k × n, status n).  Every entry is summed sequentially in
+ascending cell order from the first member's value.  Returns `(cost, grad, JtJ, status)` with n_groups columns: what `lm_step` takes for a Θt of one column per group.
+"""
+function lsq_group(m::Model, group_off::Vector{Cint}, fit)
+    n, ng = length(fit.cost), length(group_off) - 1
+    k = fit.grad === nothing ? 0 : size(fit.grad, 1)
+    cost, status = Vector{Float64}(undef, ng), Vector{Cint}(undef, ng)
+    grad = k > 0 ? Matrix{Float64}(undef, k, ng) : nothing
+    JtJ = k > 0 ? Array{Float64, 3}(undef, k, k, ng) : nothing
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve fit grad JtJ begin
+        check(ccall((:plh_lsq_group, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cvoid}),
+                    m.h, n, ng, group_off, k, fit.cost, p(fit.grad), p(fit.JtJ), fit.status,
+                    cost, p(grad), p(JtJ), status, PLH_HOST, C_NULL),
+              "plh_lsq_group")
+    end
+    (cost = cost, grad = grad, JtJ = JtJ, status = status)
+end
+
+"""
+    group_scatter!(Θt, m, group_off, cols, Θgt)
+
+`Θt[cols[i] + 1, c] = Θgt[cols[i] + 1, g]` for every member c of every group g (`plh_group_scatter`): `Θt` n_theta × n, `Θgt` n_theta × n_groups (one group per column, the
+matrix `lm_step` worked on), `cols` the 0-based θ columns of the keys.  No other entry of `Θt` is written.
+"""
+function group_scatter!(Θt::Matrix{Float64}, m::Model, group_off::Vector{Cint}, cols::Vector{Cint}, Θgt::Matrix{Float64})
+    check(ccall((:plh_group_scatter, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cvoid}),
+                m.h, size(Θt, 2), length(group_off) - 1, group_off, size(Θt, 1), length(cols), cols, Θgt, Θt, PLH_HOST, C_NULL),
+          "plh_group_scatter")
+    Θt
+end
+
 # ---- seam 1: the five generated functions of p.funcs (src/structures.jl:315-334) as single-cell evaluators ----
 function residual!(res::Vector{Float64}, m::Model, Y, YP, θ; mode = :I, value = 0.0)
     check(ccall((:plh_residual, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cvoid}),

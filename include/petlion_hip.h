@@ -532,6 +532,41 @@ int plh_lm_step(plh_model_t m, int n_cells, int n_theta, double* theta /* [n_cel
 /* sizeof / offsetof of plh_lm_opts, in plh_abi_layout's format (sizeof, number of fields, the offsets) */
 int plh_lm_abi_layout(int* out, int cap);
 
+/* ---- parameters shared by groups of cells: consecutive cells form a group (one experiment per member), all members share the fitted keys, and one group is one
+ * least-squares problem.  plh_lsq_group sums what plh_lsq_multi left per cell into one fit per group; plh_lm_step then runs with n_cells = n_groups on a matrix of one theta
+ * row per group; plh_group_scatter copies the keys of every group's row into the theta rows of its members.  A grouped fit is: scatter the start; then per iteration
+ * integrate with sensitivities, plh_lsq / plh_lsq_multi, plh_lsq_group, plh_lm_step (on the groups), plh_group_scatter.
+ *
+ * The grouping.  group_off[n_groups + 1], HOST memory for every ptr_kind (like cols): group_off[0] == 0, group_off[n_groups] == n_cells, strictly ascending (every group
+ * has at least one member).  Group g owns the cells group_off[g] .. group_off[g + 1] - 1.  The device copy of the offsets is remembered per stream: a repeated call with
+ * the same grouping uploads nothing and does not synchronise.
+ *
+ * plh_lsq_group.  For every group g with members c0 < c1 < ... :
+ *   g_cost[g]         = (..((cost[c0] + cost[c1]) + cost[c2]) + ..)
+ *   g_grad[g][i]      = the same sum of grad[c][i], for every i < n_sens
+ *   g_JtJ[g][i][j]    = the same sum of JtJ[c][i][j], for every i, j < n_sens (the full matrix, both triangles, as plh_lsq_multi writes it)
+ *   g_status[g]       = 1 if status[c] != 0 for any member, else 0 (g_status may be NULL; a NULL status is 0 everywhere)
+ *  The sum is sequential, in ascending cell order, and starts from the first member's value: a group of one member has its member's bits.  Only additions occur (nothing can
+ *  be contracted), so the bits of every output are a function of the inputs alone -- not of the launch shape, the pointer kind or the wave width -- and a plain loop on the
+ *  host reproduces them.  A NaN or an infinity of a member flows through the sum into its group (and into no other); plh_lm_step then rejects the group's trial.  The
+ *  inputs are not written.  n_sens == 0 is the cost-only call: grad, JtJ, g_grad and g_JtJ are then NULL -- and only then.
+ *
+ * plh_group_scatter.  theta[c][cols[i]] = g_theta[g][cols[i]] for every group g, every member c of g and every i < n_keys.  No other entry of theta is written; g_theta is
+ * not written.  cols[n_keys] is HOST memory.  A PLH_HOST call stages theta whole, both ways: an entry that is not written keeps its bits.
+ *
+ * Both: PLH_HOST blocks, PLH_DEVICE is asynchronous on `stream`; the bits are the same for both.
+ * PLH_E_ARG, nothing written: n_cells < 1; n_groups < 1 or > n_cells; a NULL group_off, or offsets that do not start at 0, do not end at n_cells or are not strictly
+ * ascending; (plh_lsq_group) n_sens outside 0 .. PLH_LSQ_MAX_SENS, a NULL cost or g_cost, grad / JtJ / g_grad / g_JtJ whose NULL-ness does not match n_sens;
+ * (plh_group_scatter) n_theta < 1, n_keys outside 1 .. PLH_LSQ_MAX_SENS, a NULL cols, g_theta or theta, a column outside [0, n_theta) or given twice. */
+int plh_lsq_group(plh_model_t m, int n_cells, int n_groups, const int* group_off /* [n_groups + 1], HOST */,
+                  int n_sens, const double* cost /* [n_cells] */, const double* grad /* [n_cells][n_sens] */, const double* JtJ /* [n_cells][n_sens][n_sens] */,
+                  const int* status /* [n_cells] or NULL */,
+                  double* g_cost /* [n_groups] */, double* g_grad /* [n_groups][n_sens] */, double* g_JtJ /* [n_groups][n_sens][n_sens] */,
+                  int* g_status /* [n_groups] or NULL */, int ptr_kind, void* stream);
+int plh_group_scatter(plh_model_t m, int n_cells, int n_groups, const int* group_off /* [n_groups + 1], HOST */,
+                      int n_theta, int n_keys, const int* cols /* [n_keys], HOST */,
+                      const double* g_theta /* [n_groups][n_theta] */, double* theta /* [n_cells][n_theta] */, int ptr_kind, void* stream);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

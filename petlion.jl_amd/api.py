@@ -913,6 +913,59 @@ class EnsembleFit:
         self.keys = list(keys)
         self.channels = list(channels)
         self.cost = self.grad = self.JtJ = self.resid = self.resid_I = self.resid_T_avg = self.status = None
+        self._p = self._stream = None                                    # the model and the launch stream of the ensemble (ens.lsq sets them: by_group needs them)
+
+    def by_group(self, groups):
+        """The fits of consecutive cells that share their parameters, summed into one fit per group (plh_lsq_group; csrc/plh_group.h): groups [n_cells], the label of every
+        cell's group (group_offsets).  Returns an EnsembleFit with one row per group: .cost [n_groups], .grad [n_groups, k], .JtJ [n_groups, k, k] -- every entry the sum of
+        the members' entries, taken sequentially in ascending cell order from the first member's value (a group of one has its member's bits) --, .status [n_groups] (1: a
+        member's status is not 0); resid* are None.  A fit in HBM stays there, queued on the ensemble's launch stream."""
+        off = group_offsets(groups, self.cost.shape[0])
+        ng, ns = len(off) - 1, len(self.keys)
+        out = EnsembleFit(self.keys, self.channels)
+        out._p, out._stream = self._p, self._stream
+        device = not isinstance(self.cost, np.ndarray)
+        if device:
+            import torch
+            dev = self.cost.device
+            mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
+        else:
+            mk = lambda *shape, dt=np.float64: np.empty(shape, dt)
+        out.cost, out.status = mk(ng), mk(ng, dt=torch.int32 if device else np.int32)
+        if ns:
+            out.grad, out.JtJ = mk(ng, ns), mk(ng, ns, ns)
+        ext = None
+        if device and self._stream is not None and int(self._stream) != torch.cuda.current_stream(dev).cuda_stream:
+            ext = torch.cuda.ExternalStream(int(self._stream), device=dev)      # (allocated on torch's current stream, written on the launch stream: as in ens.lsq)
+            ext.wait_stream(torch.cuda.current_stream(dev))
+        _lsq_group(self._p, off, self, out, self._stream)
+        if ext is not None:
+            for v in (out.cost, out.grad, out.JtJ, out.status):
+                if v is not None:
+                    v.record_stream(ext)
+        return out
+
+
+def group_offsets(groups, n_cells):
+    """groups [n_cells]: the integer label of every cell's group, non-decreasing from 0 without gaps (the members of a group are consecutive cells).  Returns the offsets
+    [n_groups + 1] (int32) the C ABI takes: group g owns the cells off[g] .. off[g + 1] - 1."""
+    g = np.asarray(groups.cpu() if hasattr(groups, "cpu") else groups)
+    if g.ndim != 1 or g.shape[0] != n_cells or g.shape[0] < 1:
+        raise ValueError("groups must be a 1-D array of n_cells = %d labels" % n_cells)
+    if not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("groups must be an integer array")
+    g = g.astype(np.int64)
+    d = np.diff(g)
+    if g[0] != 0 or ((d != 0) & (d != 1)).any():
+        raise ValueError("groups: the labels must start at 0 and be non-decreasing without gaps (the members of a group are consecutive cells)")
+    return np.ascontiguousarray(np.concatenate([[0], np.flatnonzero(d) + 1, [n_cells]]), dtype=np.int32)
+
+
+def _lsq_group(p, off, fit, out, stream):
+    """plh_lsq_group: the per-cell EnsembleFit `fit` summed by groups into the arrays of `out` (host arrays or tensors in HBM, like fit's)"""
+    kind = cap.PLH_HOST if isinstance(fit.cost, np.ndarray) else cap.PLH_DEVICE
+    cap.check(p._lib, p._lib.plh_lsq_group(p._h, fit.cost.shape[0], len(off) - 1, off.ctypes.data, len(fit.keys), cap.ptr(fit.cost), cap.ptr(fit.grad), cap.ptr(fit.JtJ), cap.ptr(fit.status),
+                                           cap.ptr(out.cost), cap.ptr(out.grad), cap.ptr(out.JtJ), cap.ptr(out.status), kind, stream if kind == cap.PLH_DEVICE else None), "plh_lsq_group")
 
 
 class EnsembleSolution:
@@ -1078,6 +1131,7 @@ class EnsembleSolution:
         if ext is not None:
             ext.wait_stream(torch.cuda.current_stream(dev))
         out = EnsembleFit(self.keys, [c for c, _, _ in data])
+        out._p, out._stream = self.p, stream
         out.cost, out.status = mk(n), mk(n, dt=torch.int32 if device else np.int32)
         if ns:
             out.grad, out.JtJ = mk(n, ns), mk(n, ns, ns)
@@ -1188,11 +1242,14 @@ class EnsembleFitResult:
     """fit_ensemble's result.  theta [n, n_theta]: every cell's best point; cost [n], grad [n, k], JtJ [n, k, k]: the fit at that point (NaN for a cell whose start could not
     be used); state [n] (cap.LM_*: CONV_F / CONV_X / CONV_G / MAXIT / STALLED / FAILED_START, names in cap.LM_STATE_NAMES), lam [n], n_accept [n], n_reject [n]; n_iter: the
     number of integrations; keys; history: None, or per iteration a dict of host copies (phase, theta_before / theta_after, cost, grad, JtJ, status, before / after: the
-    per-cell state arrays, n_running)."""
+    per-cell state arrays, n_running).
+    A grouped fit (fit_ensemble(groups=...)): group_off [n_groups + 1] (else None); theta stays [n, n_theta], every member holding its group's best point; every other array
+    has one row per GROUP, and so has the history (theta_before / theta_after are the [n_groups, n_theta] matrix of the groups' rows), which additionally records
+    member = dict(cost, grad, JtJ, status), the per-cell fits that were summed, and Theta, the per-cell matrix after the scatter."""
 
     def __init__(self, keys):
         self.keys = list(keys)
-        self.theta = self.cost = self.grad = self.JtJ = self.state = self.lam = self.n_accept = self.n_reject = self.history = None
+        self.theta = self.cost = self.grad = self.JtJ = self.state = self.lam = self.n_accept = self.n_reject = self.history = self.group_off = None
         self.n_iter = 0
 
 
@@ -1200,7 +1257,7 @@ LM_STATE_ARRAYS = ("theta_cur", "cost_cur", "grad_cur", "JtJ_cur", "lam", "pred"
 
 
 def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data=None, I_weights=None, T_avg_data=None, T_avg_weights=None, *, bounds=None, transform=None,
-                 max_iter=30, check_every=1, SOC=None, opts=None, lm=None, device=False, stream=None, max_points=None, interp_bc="interpolate", history=False):
+                 max_iter=30, check_every=1, SOC=None, opts=None, lm=None, device=False, stream=None, max_points=None, interp_bc="interpolate", history=False, groups=None):
     """Levenberg-Marquardt fit of every cell's `keys` to measured curves, the loop on the device: per iteration one sensitivity integration (simulate_ensemble(sens=keys)),
     ens.lsq(t, ...) and one plh_lm_step (csrc/plh_lm.h; include/petlion_hip.h states what a step does), which judges the trial, updates the damping, tests convergence, solves
     the damped, scaled, bounded normal equations and writes the next trial into Theta -- all in HBM with device=True, where the 4-byte read of the number of running cells every
@@ -1209,6 +1266,12 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
     given data are the ones differentiated).  bounds = {key: (lo, hi)}, scalars or [n_cells] arrays, None = unbounded on that side; transform = {key: "log" | "linear"} (default
     linear; log: the step is taken in ln theta, the parameter must be positive); lm = {option: value} over cap.LM_OPT_DEFAULTS.  At most max_iter + 1 integrations: the first
     point, up to max_iter - 1 steps, and one last judgement.  Cells that are done keep being integrated at their best point (the ensemble is not compacted).
+    groups [n_cells] (labels, see group_offsets): consecutive cells form a group, one experiment per member, and the members of a group SHARE the keys -- one group is one
+    least-squares problem (several C-rates, a discharge and a rest, many starts at once).  Every other column of Theta0, the protocol's per-cell inputs / tf, SOC and per-cell
+    data and weights stay per cell: that is how members differ.  A group starts at its FIRST member's values of the keys (scattered to all members before the first
+    integration).  Per iteration: the integration, ens.lsq, plh_lsq_group (the members' fits summed), plh_lm_step on the [n_groups, n_theta] matrix of the first members' rows,
+    plh_group_scatter into Theta.  A trial is judged for the group as a whole: one member whose integration failed rejects it.  Bounds are then scalars or [n_groups] arrays,
+    and every array of the result but theta has n_groups rows (EnsembleFitResult).
     Returns an EnsembleFitResult."""
     keys = list(keys)
     if len(keys) < 1 or len(keys) > cap.LSQ_MAX_SENS:
@@ -1235,6 +1298,8 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
     lmo = cap.LMOpts(**(lm or {}))
     n, nth, k = Theta0.shape[0], Theta0.shape[1], len(keys)
     cols = np.ascontiguousarray([p.θ_keys.index(kname) for kname in keys], dtype=np.int32)
+    off = None if groups is None else group_offsets(groups, n)
+    nf = n if off is None else len(off) - 1                              # the number of least-squares problems: cells, or groups
     if device:
         import torch
         dev = Theta0.device
@@ -1256,7 +1321,7 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
     blo, bhi = np.full(k, -np.inf), np.full(k, np.inf)
     per_cell = any(b is not None and np.ndim(b.cpu() if hasattr(b, "cpu") else b) > 0 for pair in (bounds or {}).values() for b in pair)
     if per_cell:
-        blo, bhi = np.full((n, k), -np.inf), np.full((n, k), np.inf)
+        blo, bhi = np.full((nf, k), -np.inf), np.full((nf, k), np.inf)
     for kname, pair in (bounds or {}).items():
         if len(pair) != 2:
             raise ValueError("fit_ensemble: bounds[%r] must be (lo, hi)" % (kname,))
@@ -1264,38 +1329,61 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
             if b is None:
                 continue
             b = np.asarray(b.cpu() if hasattr(b, "cpu") else b, dtype=np.float64)
-            if b.ndim and b.shape != (n,):
-                raise ValueError("fit_ensemble: a bound of %r must be a scalar or [n_cells]" % (kname,))
+            if b.ndim and b.shape != (nf,):
+                raise ValueError("fit_ensemble: a bound of %r must be a scalar or [%s]" % (kname, "n_cells" if off is None else "n_groups"))
             dst[..., keys.index(kname)] = b
     if per_cell and device:
         lo_a, hi_a = torch.as_tensor(blo).to(dev), torch.as_tensor(bhi).to(dev)
     else:
         lo_a, hi_a = np.ascontiguousarray(blo), np.ascontiguousarray(bhi)
-    st = dict(theta_cur=mk((n, k)), cost_cur=mk((n,)), grad_cur=mk((n, k)), JtJ_cur=mk((n, k, k)), lam=mk((n,)), pred=mk((n,)), state=mki((n,)), n_accept=mki((n,)), n_reject=mki((n,)))
+    st = dict(theta_cur=mk((nf, k)), cost_cur=mk((nf,)), grad_cur=mk((nf, k)), JtJ_cur=mk((nf, k, k)), lam=mk((nf,)), pred=mk((nf,)), state=mki((nf,)), n_accept=mki((nf,)), n_reject=mki((nf,)))
     n_running = mki((1,))
+    LTheta, gfit = Theta, None                                           # the matrix plh_lm_step works on: one row per problem
+    if off is not None:                                                  # the groups' rows (their first members') and the groups' fit: allocated once, before the loop
+        first = off[:-1].astype(np.int64)
+        LTheta = Theta[torch.as_tensor(first).to(dev)].contiguous() if device else np.ascontiguousarray(Theta[first])
+        gfit = EnsembleFit(keys, given)
+        gfit.cost, gfit.grad, gfit.JtJ, gfit.status = mk((nf,)), mk((nf, k)), mk((nf, k, k)), mki((nf,))
     ext = None
     if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
         ext = torch.cuda.ExternalStream(int(stream), device=dev)         # (made on torch's current stream, used on the launch stream: as in _integrate)
         ext.wait_stream(torch.cuda.current_stream(dev))
-        for v in [Theta, n_running, lo_a, hi_a] + list(st.values()):
+        for v in [Theta, n_running, lo_a, hi_a] + list(st.values()) + ([] if off is None else [LTheta, gfit.cost, gfit.grad, gfit.JtJ, gfit.status]):
             if hasattr(v, "record_stream"):
                 v.record_stream(ext)
     res = EnsembleFitResult(keys)
     res.history = [] if history else None
     lib, h = p._lib, p._h
 
+    def scatter():                                                       # the keys of every group's row into the rows of its members
+        cap.check(lib, lib.plh_group_scatter(h, n, nf, off.ctypes.data, nth, k, cols.ctypes.data, cap.ptr(LTheta), cap.ptr(Theta), kind, stream), "plh_group_scatter")
+
+    if off is not None:
+        res.group_off = off
+        scatter()                                                        # (the start is consistent by construction)
+
     def iteration(phase):
         ens = simulate_ensemble(p, Theta, protocol, SOC=SOC, opts=opts, device=device, stream=stream, max_points=max_points, YP=False, sens=keys, sens_outputs=tuple(given))
         fit = ens.lsq(t, V_data, weights, interp_bc=interp_bc, I_data=I_data, I_weights=I_weights, T_avg_data=T_avg_data, T_avg_weights=T_avg_weights)
+        if off is not None:
+            member = fit
+            _lsq_group(p, off, member, gfit, stream)
+            fit = gfit
         if history:
-            rec = dict(phase=phase, theta_before=host(Theta), cost=host(fit.cost), grad=host(fit.grad), JtJ=host(fit.JtJ), status=host(fit.status), before={a: host(v) for a, v in st.items()})
-        cap.check(lib, lib.plh_lm_step(h, n, nth, cap.ptr(Theta), k, cols.ctypes.data, tf.ctypes.data, cap.ptr(lo_a), cap.ptr(hi_a), 1 if per_cell else 0,
+            rec = dict(phase=phase, theta_before=host(LTheta), cost=host(fit.cost), grad=host(fit.grad), JtJ=host(fit.JtJ), status=host(fit.status), before={a: host(v) for a, v in st.items()})
+            if off is not None:
+                rec["member"] = dict(cost=host(member.cost), grad=host(member.grad), JtJ=host(member.JtJ), status=host(member.status))
+        cap.check(lib, lib.plh_lm_step(h, nf, nth, cap.ptr(LTheta), k, cols.ctypes.data, tf.ctypes.data, cap.ptr(lo_a), cap.ptr(hi_a), 1 if per_cell else 0,
                                        cap.ptr(fit.cost), cap.ptr(fit.grad), cap.ptr(fit.JtJ), cap.ptr(fit.status),
                                        cap.ptr(st["theta_cur"]), cap.ptr(st["cost_cur"]), cap.ptr(st["grad_cur"]), cap.ptr(st["JtJ_cur"]), cap.ptr(st["lam"]), cap.ptr(st["pred"]),
                                        cap.ptr(st["state"]), cap.ptr(st["n_accept"]), cap.ptr(st["n_reject"]), C.byref(lmo), phase, cap.ptr(n_running), kind, stream), "plh_lm_step")
         res.n_iter += 1
+        if off is not None:
+            scatter()
         if history:
-            rec.update(theta_after=host(Theta), after={a: host(v) for a, v in st.items()}, n_running=int(host(n_running)[0]))
+            rec.update(theta_after=host(LTheta), after={a: host(v) for a, v in st.items()}, n_running=int(host(n_running)[0]))
+            if off is not None:
+                rec["Theta"] = host(Theta)
             res.history.append(rec)
 
     read_running = lambda: int(host(n_running)[0])                       # (device=True: the loop's only synchronisation)

@@ -37,6 +37,7 @@
 #include "plh_resample.h"
 #include "plh_lsq.h"
 #include "plh_lm.h"
+#include "plh_group.h"
 
 using namespace pl;
 
@@ -189,6 +190,7 @@ struct StreamCtx {
   Uploaded<int> sel;                                        // packed entry -> state index of plh_outputs.sel (Y_sel); allocated at N ints, the longest selection there is
   DevBuf resample;                                          // plh_resample: elimination factors, query locations and slopes of one chunk of cells (plh_resample.h, plrs::Work)
   Uploaded<double> lm_bounds;                               // plh_lm_step: shared bounds, lo[n_keys] then hi[n_keys] (remembered: the same for every iteration of a fit)
+  Uploaded<int> group_off;                                  // plh_lsq_group / plh_group_scatter: the offsets of the groups (remembered: the same for every iteration of a grouped fit)
   Uploaded<double> resample_tq;                             // plh_resample: the query times (remembered: the fields of one ensemble are resampled on the same grid, one call each)
   hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
   std::vector<hipEvent_t> ret_ev;                           // one event per output array of a synchronous host call (host_return): grown on demand, kept
@@ -581,7 +583,7 @@ void plh_model_destroy(plh_model_t m) {
   for (void* p : m->d_tables) hipFree(p);
   if (m->d_tb) hipFree(m->d_tb);
   for (StreamCtx* c : m->streams) {
-    for (DevBuf* b : {&c->scratch, &c->genW, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf, &c->resample, &c->resample_tq.buf}) b->free();
+    for (DevBuf* b : {&c->scratch, &c->genW, &c->runs.buf, &c->tdiscon.buf, &c->tstops.buf, &c->sel.buf, &c->resample, &c->resample_tq.buf, &c->lm_bounds.buf, &c->group_off.buf}) b->free();
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->ret_ev) hipEventDestroy(e);
@@ -1416,6 +1418,67 @@ int plh_lm_step(plh_model_t m, int n, int n_theta, double* theta, int n_keys, co
   s.back(theta, A.theta, nth); s.back(theta_cur, A.theta_cur, nk); s.back(cost_cur, A.cost_cur, nn); s.back(grad_cur, A.grad_cur, nk); s.back(JtJ_cur, A.JtJ_cur, nkk);
   s.back(lambda, A.lambda, nn); s.back(pred, A.pred, nn); s.back(state, A.state, nn); s.back(n_accept, A.n_accept, nn); s.back(n_reject, A.n_reject, nn);
   s.back(n_running, d_count, 1);
+  CHECK_STAGE(s);
+  return 0;
+}
+
+// ---- plh_lsq_group / plh_group_scatter: parameters shared by groups of consecutive cells (kernels: plh_group.h).  The offsets and cols are host memory; the offsets' device
+// copy is remembered per stream like the shared LM bounds: from the second iteration of a fit on nothing is uploaded and nothing synchronises ----
+static int check_groups(const char* who, int n, int n_groups, const int* group_off) {
+  if (n < 1) return fail(PLH_E_ARG, std::string(who) + ": n_cells must be >= 1");
+  if (n_groups < 1 || n_groups > n) return fail(PLH_E_ARG, std::string(who) + ": n_groups must be 1 .. n_cells");
+  if (!group_off) return fail(PLH_E_ARG, std::string(who) + ": null group_off");
+  if (group_off[0] != 0 || group_off[n_groups] != n) return fail(PLH_E_ARG, std::string(who) + ": group_off must start at 0 and end at n_cells");
+  for (int g = 0; g < n_groups; g++) if (!(group_off[g] < group_off[g + 1])) return fail(PLH_E_ARG, std::string(who) + ": group_off must be strictly ascending (every group has a member)");
+  return 0;
+}
+int plh_lsq_group(plh_model_t m, int n, int n_groups, const int* group_off, int n_sens, const double* cost, const double* grad, const double* JtJ, const int* status,
+                  double* g_cost, double* g_grad, double* g_JtJ, int* g_status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (int rc = check_groups("plh_lsq_group", n, n_groups, group_off)) return rc;
+  if (n_sens < 0 || n_sens > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_lsq_group: n_sens must be 0 .. PLH_LSQ_MAX_SENS (8)");
+  if (!cost || !g_cost) return fail(PLH_E_ARG, "plh_lsq_group: null array (only status and g_status may be NULL)");
+  if ((n_sens > 0) != (grad != nullptr) || (n_sens > 0) != (JtJ != nullptr) || (n_sens > 0) != (g_grad != nullptr) || (n_sens > 0) != (g_JtJ != nullptr))
+    return fail(PLH_E_ARG, "plh_lsq_group: grad, JtJ, g_grad and g_JtJ are given with n_sens > 0 and NULL with n_sens == 0");
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  const size_t nn = (size_t)n, ng = (size_t)n_groups, ns = (size_t)n_sens;
+  plgr::SumArgs A;
+  A.n_sens = n_sens;
+  A.cost = s.in(cost, nn); A.grad = s.in(grad, nn * ns); A.JtJ = s.in(JtJ, nn * ns * ns); A.status = s.in(status, nn);
+  A.g_cost = s.buf(g_cost, ng, false); A.g_grad = s.buf(g_grad, ng * ns, false); A.g_JtJ = s.buf(g_JtJ, ng * ns * ns, false); A.g_status = s.buf(g_status, ng, false);
+  CHECK_STAGE(s);
+  if (int rc = s.cx->group_off.get(s.cx->st, std::vector<int>(group_off, group_off + n_groups + 1), &A.group_off)) return rc;
+  plgr::launch_sum(s.st, n_groups, A);
+  FINISH(s);
+  s.back(g_cost, A.g_cost, ng); s.back(g_grad, A.g_grad, ng * ns); s.back(g_JtJ, A.g_JtJ, ng * ns * ns); s.back(g_status, A.g_status, ng);
+  CHECK_STAGE(s);
+  return 0;
+}
+int plh_group_scatter(plh_model_t m, int n, int n_groups, const int* group_off, int n_theta, int n_keys, const int* cols, const double* g_theta, double* theta, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (int rc = check_groups("plh_group_scatter", n, n_groups, group_off)) return rc;
+  if (n_theta < 1) return fail(PLH_E_ARG, "plh_group_scatter: n_theta must be >= 1");
+  if (n_keys < 1 || n_keys > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_group_scatter: n_keys must be 1 .. PLH_LSQ_MAX_SENS (8)");
+  if (!cols || !g_theta || !theta) return fail(PLH_E_ARG, "plh_group_scatter: null array");
+  plgr::ScatterArgs A;
+  for (int i = 0; i < plgr::NK; i++) A.cols[i] = 0;
+  for (int i = 0; i < n_keys; i++) {
+    if (cols[i] < 0 || cols[i] >= n_theta) return fail(PLH_E_ARG, "plh_group_scatter: a column outside [0, n_theta)");
+    for (int j = 0; j < i; j++) if (cols[j] == cols[i]) return fail(PLH_E_ARG, "plh_group_scatter: a column given twice");
+    A.cols[i] = cols[i];
+  }
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  const size_t nth = (size_t)n * n_theta;
+  A.n_theta = n_theta; A.n_keys = n_keys;
+  A.g_theta = s.in(g_theta, (size_t)n_groups * n_theta);
+  A.theta = s.buf(theta, nth, true);                                   // (whole, both ways: an entry that is not written keeps its bits)
+  CHECK_STAGE(s);
+  if (int rc = s.cx->group_off.get(s.cx->st, std::vector<int>(group_off, group_off + n_groups + 1), &A.group_off)) return rc;
+  plgr::launch_scatter(s.st, n_groups, A);
+  FINISH(s);
+  s.back(theta, A.theta, nth);
   CHECK_STAGE(s);
   return 0;
 }

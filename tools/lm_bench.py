@@ -10,7 +10,16 @@ Shape: the C4 shard (8192 jittered cells, 1C discharge), the seven sweep paramet
                      handling; timed the same way, alternating with lm_step
   sens_integration   the sensitivity kernel of one iteration (plh_last_kernel_ms)
   fit                one fit_ensemble from starts at 2^(+-0.25) of the truth in the seven keys: per iteration the number of cells still running before it, and from that the
-                     share of cell-integrations spent on cells already done (the ensemble is not compacted)"""
+                     share of cell-integrations spent on cells already done (the ensemble is not compacted)
+
+  python tools/lm_bench.py --groups [--out profiles/lm_groups.json]          parameters shared by groups of cells (plh_lsq_group, plh_group_scatter, fit_ensemble(groups=...))
+  group_calls        plh_lsq_group + plh_group_scatter on the fit ens.lsq left in HBM (the C4-shard shape, seven keys), HIP events around the two calls, median of --reps after a
+                     warm-up; 2048 groups of 4 and 1 group of 8192; alternating in the same process with the torch composition of the same result (index_add_ /
+                     repeat_interleave: another order of summation, no definition of the bits)
+  fits               the seven keys from starts at 2^(+-0.25) of the truth, max_iter as above: 2048 groups of 4 members at 0.5C / 1C / 2C / 3C against 8192 single 1C cells,
+                     the same number of data per problem (200: the groups' members have 50 each) with 2 mV of noise; the final states, cond of the final JtJ in log
+                     parameters, and how far the best point is from the truth
+  bench_c2_same_box  with --c2-line FILE: the line `bench.py --gpus 1` printed on the same box (the integrator is untouched by the grouping)"""
 import argparse
 import json
 import os
@@ -31,7 +40,13 @@ def main():
     ap.add_argument("--points", type=int, default=200)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--max-iter", type=int, default=12)
+    ap.add_argument("--groups", action="store_true", help="measure the grouped calls and the grouped fit instead (default --out: profiles/lm_groups.json)")
+    ap.add_argument("--c2-line", default=None, help="--groups: a file whose last line is the JSON line `bench.py --gpus 1` printed on the same box; kept in the record as bench_c2_same_box")
     a = ap.parse_args()
+    if a.groups:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "lm_groups.json")
+        return main_groups(a)
     import torch
     assert torch.cuda.is_available(), "tools/lm_bench.py measures on a GPU"
     import pkgload
@@ -114,6 +129,127 @@ def main():
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(rec, open(a.out, "w"), indent=1)
     print(json.dumps({x: rec[x] for x in ("lm_step", "torch_composition", "lm_step_over_torch_composition", "sens_integration", "fit")}))
+
+
+def main_groups(a):
+    import torch
+    assert torch.cuda.is_available(), "tools/lm_bench.py measures on a GPU"
+    import pkgload
+    pkg = pkgload.load()
+    cap = pkg._capi
+    p = pkg.petlion(pkg.LCO)
+    lib, h = p._lib, p._h
+    n, n_q = a.cells, a.points
+    keys = [k for k in pkg.configs.SWEEP_KEYS if k in p.θ_keys]
+    k = len(keys)
+    cols = np.ascontiguousarray([p.θ_keys.index(x) for x in keys], dtype=np.int32)
+    cols_t = torch.from_numpy(cols.astype(np.int64)).cuda()
+    nth = len(p.θ_keys)
+    rng = np.random.default_rng(0)
+
+    # ---- (a) the two calls on the C4-shard fit
+    cfg = pkg.configs.c4(p, n)
+    Th = torch.from_numpy(cfg["theta"]).cuda()
+    ens = pkg.simulate_ensemble(p, Th, cfg["protocol"], SOC=cfg["SOC"], device=True, max_points=cfg["max_points"], sens=keys)
+    torch.cuda.synchronize()
+    tq = np.linspace(0.0, float(ens.run_info["t_end"][:, -1].min()), n_q)
+    data = ens(tq, fields="V").V[0] + torch.from_numpy(2e-3 * rng.standard_normal(n_q)).cuda()
+    w = torch.full((n_q,), 1 / 2e-3, dtype=torch.float64, device="cuda")
+    fit = ens.lsq(tq, data, weights=w)
+    ms_s = []
+    for _ in range(3):
+        e = pkg.simulate_ensemble(p, Th, cfg["protocol"], SOC=cfg["SOC"], device=True, max_points=cfg["max_points"], sens=keys); torch.cuda.synchronize(); ms_s.append(float(e.kernel_ms))
+    calls = {}
+    for name, sizes in (("%d_groups_of_4" % (n // 4), [4] * (n // 4)), ("1_group_of_%d" % n, [n])):
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int32)
+        ng = len(sizes)
+        lab = torch.from_numpy(np.repeat(np.arange(ng), sizes)).cuda()
+        counts = torch.from_numpy(np.asarray(sizes)).cuda()
+        mk = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device="cuda")
+        g = dict(cost=mk(ng), grad=mk(ng, k), JtJ=mk(ng, k, k), status=mk(ng, dt=torch.int32))
+        g_theta, theta = Th[torch.from_numpy(off[:-1].astype(np.int64)).cuda()].contiguous(), Th.clone()
+        theta2 = Th.clone()
+
+        def ours():
+            cap.check(lib, lib.plh_lsq_group(h, n, ng, off.ctypes.data, k, fit.cost.data_ptr(), fit.grad.data_ptr(), fit.JtJ.data_ptr(), fit.status.data_ptr(),
+                                             g["cost"].data_ptr(), g["grad"].data_ptr(), g["JtJ"].data_ptr(), g["status"].data_ptr(), cap.PLH_DEVICE, None), "plh_lsq_group")
+            cap.check(lib, lib.plh_group_scatter(h, n, ng, off.ctypes.data, nth, k, cols.ctypes.data, g_theta.data_ptr(), theta.data_ptr(), cap.PLH_DEVICE, None), "plh_group_scatter")
+
+        def torch_composition():
+            c = mk(ng).index_add_(0, lab, fit.cost); gr = mk(ng, k).index_add_(0, lab, fit.grad); H = mk(ng, k, k).index_add_(0, lab, fit.JtJ)
+            s = mk(ng, dt=torch.int32).index_add_(0, lab, (fit.status != 0).to(torch.int32)) > 0
+            theta2[:, cols_t] = torch.repeat_interleave(g_theta[:, cols_t], counts, dim=0)
+            return c, gr, H, s
+
+        ours(); tc = torch_composition(); torch.cuda.synchronize()                # warm-up of both
+        rel = float(((tc[2] - g["JtJ"]).abs().amax() / g["JtJ"].abs().amax()).cpu())
+        assert torch.equal(theta, theta2) and rel < 1e-9, rel
+        ms_k, ms_t = [], []
+        for _ in range(a.reps):
+            ms_k.append(timed(ours)[0])
+            ms_t.append(timed(torch_composition)[0])
+        calls[name] = {"groups": ng, "plh_lsq_group_and_scatter": spread(ms_k), "torch_composition": spread(ms_t), "ours_over_torch_composition": float(np.median(ms_k) / np.median(ms_t)),
+                       "ours_over_sens_integration": float(np.median(ms_k) / np.median(ms_s)), "JtJ_rel_difference_to_torch_composition": rel}
+
+    # ---- (b) the fit the grouping is for
+    rates = [0.5, 1.0, 2.0, 3.0]
+    truth = pkg.theta_matrix(p, 1)
+    names = cap.LM_STATE_NAMES
+    tf = {x: "log" for x in keys}
+    t_end = {}
+    for r in rates:
+        e = pkg.simulate_ensemble(p, torch.from_numpy(truth).cuda(), [{"I": -r}], SOC=1.0, device=True, max_points=512)
+        torch.cuda.synchronize()
+        t_end[r] = float(e.run_info["t_end"][0, -1])
+
+    def problem(member_rates, n_groups):
+        """n_groups problems whose members run at member_rates; n_q data per problem, shared evenly among the members"""
+        m = len(member_rates)
+        per = n_q // m
+        tq = np.concatenate([np.linspace(0.0, 0.95 * t_end[r], per) for r in member_rates])
+        I = np.tile([-r for r in member_rates], n_groups)
+        proto = [{"I": I}]
+        Th1 = torch.from_numpy(np.repeat(truth, m, axis=0)).cuda()
+        e = pkg.simulate_ensemble(p, Th1, [{"I": np.asarray([-r for r in member_rates])}], SOC=1.0, device=True, max_points=512)
+        V = e(tq, fields="V").V.cpu().numpy()                                   # [m, n_q]: the truth at every member's rate
+        wm = np.zeros((m, len(tq)))
+        for j in range(m):
+            wm[j, j * per:(j + 1) * per] = 1 / 2e-3
+        V = np.where(wm > 0, V, 0.0)
+        data = np.tile(V, (n_groups, 1)) + 2e-3 * rng.standard_normal((n_groups * m, len(tq)))
+        start = np.repeat(truth, n_groups * m, axis=0)
+        start[:, cols] *= np.repeat(2.0 ** rng.uniform(-0.25, 0.25, size=(n_groups, k)), m, axis=0)
+        return proto, tq, torch.from_numpy(data).cuda(), torch.from_numpy(np.tile(wm, (n_groups, 1))).cuda(), torch.from_numpy(start).cuda(), m
+
+    def run(member_rates, n_groups, grouped):
+        proto, tq, data, wts, start, m = problem(member_rates, n_groups)
+        groups = np.repeat(np.arange(n_groups), m) if grouped else None
+        t0 = timed(lambda: pkg.fit_ensemble(p, start, proto, keys, tq, data, wts, SOC=1.0, max_points=512, transform=tf, max_iter=a.max_iter, device=True, history=False, groups=groups))
+        ms, res = t0
+        state = res.state.cpu().numpy()
+        th = res.theta.cpu().numpy()[::m][:, cols]                              # a group's point: its first member's
+        s = th[:, :, None] * th[:, None, :]
+        H = res.JtJ.cpu().numpy() * s                                           # in log parameters
+        ok = np.isfinite(H).all(axis=(1, 2))
+        cond = np.full(len(H), np.nan)
+        cond[ok] = np.linalg.cond(H[ok])
+        err = np.abs(th / truth[0, cols] - 1).max(axis=1)
+        q = lambda x: {"p10": float(np.nanpercentile(x, 10)), "median": float(np.nanmedian(x)), "p90": float(np.nanpercentile(x, 90))}
+        conv = int(np.isin(state, (cap.LM_CONV_F, cap.LM_CONV_X, cap.LM_CONV_G)).sum())
+        return {"problems": int(len(state)), "cells": int(len(state) * m), "members_at_C_rates": member_rates, "data_per_problem": int(m * (n_q // m)), "integrations": res.n_iter,
+                "fit_ms": float(ms), "converged": conv, "stalled": int((state == cap.LM_STALLED).sum()), "still_descending_at_max_iter": int((state == cap.LM_MAXIT).sum()),
+                "final_states": {names[x]: int((state == x).sum()) for x in range(len(names))}, "cond_JtJ_log_parameters": q(cond),
+                "max_over_keys_of_abs_theta_over_truth_minus_1": q(err), "cost": q(res.cost.cpu().numpy())}
+
+    fits = {"groups_of_4": run(rates, n // 4, True), "single_1C_cells": run([1.0], n, False)}
+    rec = {"cells": n, "n_q": n_q, "keys": keys, "transform": "log", "max_iter": a.max_iter, "sens_integration": spread(ms_s), "group_calls": calls, "fits": fits,
+           "build_info": p._lib.plh_build_info().decode()}
+    if a.c2_line:                                                               # the integrator of the same binary on the same box
+        b = json.loads([line for line in open(a.c2_line) if line.startswith('{"metric"')][-1])
+        rec["bench_c2_same_box"] = dict({x: b[x] for x in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step")}, kernel_ms_avg=b["roofline"]["kernel_ms_avg"])
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(rec, open(a.out, "w"), indent=1)
+    print(json.dumps(rec))
 
 
 if __name__ == "__main__":
