@@ -502,6 +502,42 @@ function fit_ensemble(m::Model, p, Θ0::Matrix{Float64}, protocol, keys::Vector{
     (θ = permutedims(Θt), cost = st.cost_cur, grad = st.grad_cur, JtJ = st.JtJ_cur, state = st.state, λ = st.λ, n_accept = st.n_accept, n_reject = st.n_reject, n_iter = n_iter)
 end
 
+const COV_BAD_INPUT, COV_NO_FREE, COV_UNSEEN, COV_NO_DOF, COV_SINGULAR, COV_SWEEPS = Cint(1), Cint(2), Cint(4), Cint(8), Cint(16), Cint(32)      # bits of fit_cov's status
+
+"""
+    fit_cov(m, θ_k, transform, cost, grad, JtJ; n_data = nothing, lo = nothing, hi = nothing)
+
+Parameter covariances and identifiability of n fitted problems (`plh_fit_cov`; include/petlion_hip.h states the definition).  `θ_k` k × n (the keys' values: `st.θ_cur`),
+`cost` n, `grad` k × n, `JtJ` k × k × n: what a fit left behind (`LMState`, or `lsq_multi` / `lsq_group`).  `transform` `LM_LINEAR` / `LM_LOG` per key, `lo` / `hi` as
+`lm_step` takes them.  `n_data` (Vector{Cint}, the number of data of every problem): the residual variance is 2 cost / (n_data - n_free); `nothing`: σ² = 1.  Returns
+`(σ2, cov, stderr, corr, eval, evec, collinearity, free, status)`: `cov`, `corr` k × k × n, `stderr`, `eval` k × n, `evec` k × k × n with `evec[:, j, c]` eigenvector j of
+problem c (ascending eigenvalues of the normalised information matrix), `collinearity` n, `free` (bit i - 1: key i is not held) and `status` (0, or `COV_*` bits) n.
+"""
+function fit_cov(m::Model, θ_k::Matrix{Float64}, transform::Vector{Cint}, cost::Vector{Float64}, grad::Matrix{Float64}, JtJ::Array{Float64, 3};
+                 n_data = nothing, lo = nothing, hi = nothing)
+    k, n = size(θ_k)
+    per_cell = (lo !== nothing && ndims(lo) == 2) || (hi !== nothing && ndims(hi) == 2)
+    full(b) = b === nothing ? nothing : (per_cell && ndims(b) == 1 ? repeat(b, 1, n) : Array{Float64}(b))
+    l, h = full(lo), full(hi)
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    nd = n_data === nothing ? nothing : Vector{Cint}(n_data)
+    σ2, cov, se, corr = fill(NaN, n), fill(NaN, k, k, n), fill(NaN, k, n), fill(NaN, k, k, n)
+    ev, evec, coll = fill(NaN, k, n), fill(NaN, k, k, n), fill(NaN, n)
+    free, status = zeros(Cint, n), zeros(Cint, n)
+    GC.@preserve l h nd begin
+        check(ccall((:plh_fit_cov, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Cint, Ptr{Cvoid}),
+                    m.h, n, k, transform, θ_k, p(l), p(h), per_cell ? 1 : 0,
+                    cost, grad, JtJ, nd === nothing ? Ptr{Cint}(C_NULL) : pointer(nd),
+                    σ2, cov, se, corr, ev, evec, coll, free, status, PLH_HOST, C_NULL),
+              "plh_fit_cov")
+    end
+    # (C writes evec[c][j][i], component i of eigenvector j: in Julia's column-major view of the same memory that is evec[i, j, c])
+    (σ2 = σ2, cov = cov, stderr = se, corr = corr, eval = ev, evec = evec, collinearity = coll, free = free, status = status)
+end
+
 # ---- parameters shared by groups of consecutive cells (plh_lsq_group, plh_group_scatter; include/petlion_hip.h states the definition) ----
 """
     lsq_group(m, group_off, fit)

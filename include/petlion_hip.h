@@ -567,6 +567,60 @@ int plh_group_scatter(plh_model_t m, int n_cells, int n_groups, const int* group
                       int n_theta, int n_keys, const int* cols /* [n_keys], HOST */,
                       const double* g_theta /* [n_groups][n_theta] */, double* theta /* [n_cells][n_theta] */, int ptr_kind, void* stream);
 
+/* ---- parameter covariances and identifiability of n fitted problems (a problem: a cell, or a group row of a grouped fit), from the arrays a fit left behind: the *_cur
+ * state arrays of plh_lm_step, or what plh_lsq_multi / plh_lsq_group wrote together with the keys' values.  One call for all problems; nothing of the inputs is written.
+ *
+ * Arguments.  k = n_keys (1 .. PLH_LSQ_MAX_SENS).  transform[k] and shared bounds are HOST memory for every ptr_kind, every other array follows ptr_kind.
+ *   theta_k[n][k]       the keys' values, in the order of the keys (plh_lm_step's theta_cur)
+ *   lo, hi, bounds_per_cell     as plh_lm_step: [k] in HOST memory (0) or [n][k] following ptr_kind (1); a NULL lo is -inf, a NULL hi is +inf (an infinite bound is no bound)
+ *   cost[n], grad[n][k], JtJ[n][k][k]     the fit at theta_k; only JtJ's upper triangle (row <= column) is used
+ *   n_data[n]           the number of data of every problem (the (channel, time) pairs with a weight that is not 0), or NULL
+ *   sigma2[n], cov[n][k][k], stderr_[n][k], corr[n][k][k], eval[n][k], evec[n][k][k], collinearity[n], free_mask[n], status[n]     the outputs, all required
+ *
+ * Per problem ("finite": neither NaN nor +-inf; g, H: grad and the upper triangle of JtJ mirrored; theta_i: theta_k[i]):
+ *  Input check.  The input is bad if cost, a g_i, an H_ij or a theta_i is not finite, or not (lo_i <= theta_i <= hi_i) (so a NaN bound, or lo_i > hi_i, is bad input), or
+ *    theta_i <= 0 under PLH_LM_LOG, or a scaled gs_i / Hs_ij (below) is not finite, or an Hs_ii < 0.  Bad input: status = PLH_COV_BAD_INPUT, free_mask = 0, and every double
+ *    output of the problem is NaN.
+ *  Scaling and active set, plh_lm_step's:  s_i = theta_i for a LOG key, 1 for a LINEAR key; gs_i = s_i g_i; Hs_ij = (s_i s_j) H_ij.  Key i is held if
+ *    (theta_i <= lo_i and gs_i > 0) or (theta_i >= hi_i and gs_i < 0); the others are free.  free_mask: bit i is set for a free key; n_free = popcount(free_mask).
+ *  Unseen keys.  A free key with Hs_ii == 0 is unseen (the data do not move it): it is taken out of the matrices like a held key but stays in free_mask.  The mask of the
+ *    unseen keys is reported in bits 8 .. 15 of status, and PLH_COV_UNSEEN is set.  The analysed keys are the free keys that are seen; n_an is their number.
+ *  Residual variance.  n_data == NULL: sigma2 = 1 (the weights are 1 / sigma of the data: scipy's absolute_sigma).  Otherwise sigma2 = (2 cost) / (n_data - n_free); with
+ *    n_data - n_free <= 0: sigma2 = NaN and PLH_COV_NO_DOF is set (cov and stderr of the analysed keys are then NaN; corr and the eigen outputs stay valid).
+ *  Normalised information matrix.  r_i = sqrt(Hs_ii); C_ij = Hs_ij / (r_i r_j) over the analysed keys, C_ii = 1 exactly; every other key has an identity row and column.
+ *    (Marquardt's scaling, the scale plh_lm_step damps in; invariant under a change of units of a LINEAR key.)
+ *  Covariance.  Cholesky C = L L^T, row by row; a pivot that is <= 0 or not finite fails: PLH_COV_SINGULAR is set and cov, stderr and corr of the analysed keys are NaN
+ *    (the eigen outputs are still given).  Otherwise X = L^-1 (column by column), P = X^T X = C^-1, and for analysed i, j:
+ *      corr_ij = P_ij / sqrt(P_ii P_jj), corr_ii = 1 exactly;   cov_ij = (s_i s_j) ((P_ij sigma2) / (r_i r_j))   (the covariance in u, carried to theta by the delta method);
+ *      stderr_i = sqrt(cov_ii).
+ *    A held key: its rows and columns of cov and corr are 0 (the diagonal too) and stderr_i = 0.  An unseen key: its rows and columns are NaN, except where they meet a held
+ *    key (0), and stderr_i = +inf.  Both triangles are written.
+ *  Identifiability.  The eigen-decomposition of C by cyclic Jacobi, pivots (p, q), p < q, row-wise, V = I at the start.  An entry with
+ *    |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|) is set to 0 and not rotated (so an exact 0 is never rotated, and the keys that are not analysed keep unit vectors).  Otherwise
+ *    Rutishauser's rotation: theta = (a_qq - a_pp) / (2 a_pq); t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) (sign(0) = +1); c = 1 / sqrt(t^2 + 1); s = t c;
+ *    tau = s / (1 + c); a_pp -= t a_pq; a_qq += t a_pq; a_pq = 0; every other pair (g, h) = (a_rp, a_rq), and every (v_rp, v_rq): g' = g - s (h + tau g), h' = h + s (g - tau h).
+ *    The iteration stops after a sweep without a rotation; after PLH_COV_MAX_SWEEPS sweeps that all rotated, PLH_COV_SWEEPS is set.
+ *    eval[0 .. n_an - 1]: the eigenvalues (the diagonal) of the analysed part, ascending; ties keep the order of the Jacobi columns.  evec[j][.]: eigenvector j over the k keys
+ *    in key order; the component of a key that is not analysed is exactly 0; the component of largest magnitude is positive (the lowest index wins a tie).  Rows j >= n_an of
+ *    eval and evec are NaN.  collinearity = 1 / sqrt(eval[0]) (Brun et al.'s collinearity index), +inf if eval[0] <= 0; with n_an == 0 it is NaN and PLH_COV_NO_FREE is set.
+ * Nothing in the arithmetic depends on the launch shape or the pointer kind: the bits of every output are the same for PLH_HOST (blocks) and PLH_DEVICE (asynchronous on
+ * `stream`).
+ * PLH_E_ARG, nothing written: n < 1; n_keys outside 1 .. PLH_LSQ_MAX_SENS; an unknown transform; bounds_per_cell not 0 / 1; a NULL among transform, theta_k, cost, grad, JtJ
+ * and the outputs; shared bounds with lo_i > hi_i or a NaN. */
+#define PLH_COV_BAD_INPUT 1    /* status bits */
+#define PLH_COV_NO_FREE 2      /* no analysed key */
+#define PLH_COV_UNSEEN 4       /* a free key with Hs_ii == 0; which: bits 8 .. 15 */
+#define PLH_COV_NO_DOF 8       /* n_data - n_free <= 0 */
+#define PLH_COV_SINGULAR 16    /* the Cholesky factorisation of C failed */
+#define PLH_COV_SWEEPS 32      /* Jacobi still rotated in sweep PLH_COV_MAX_SWEEPS */
+#define PLH_COV_MAX_SWEEPS 16
+int plh_fit_cov(plh_model_t m, int n, int n_keys, const int* transform /* [k], HOST */,
+                const double* theta_k /* [n][k] */, const double* lo, const double* hi, int bounds_per_cell,
+                const double* cost /* [n] */, const double* grad /* [n][k] */, const double* JtJ /* [n][k][k] */, const int* n_data /* [n] or NULL */,
+                double* sigma2 /* [n] */, double* cov /* [n][k][k] */, double* stderr_ /* [n][k] */, double* corr /* [n][k][k] */,
+                double* eval /* [n][k] */, double* evec /* [n][k][k] */, double* collinearity /* [n] */,
+                int* free_mask /* [n] */, int* status /* [n] */, int ptr_kind, void* stream);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

@@ -28,6 +28,9 @@ LM_FIRST, LM_STEP, LM_LAST = 0, 1, 2
 LM_RUNNING, LM_CONV_F, LM_CONV_X, LM_CONV_G, LM_MAXIT, LM_STALLED, LM_FAILED_START = 0, 1, 2, 3, 4, 5, 6
 LM_MAX_TRIES = 16
 LM_STATE_NAMES = ["RUNNING", "CONV_F", "CONV_X", "CONV_G", "MAXIT", "STALLED", "FAILED_START"]
+COV_BAD_INPUT, COV_NO_FREE, COV_UNSEEN, COV_NO_DOF, COV_SINGULAR, COV_SWEEPS = 1, 2, 4, 8, 16, 32      # plh_fit_cov: bits of status (bits 8 .. 15: the mask of the unseen keys)
+COV_MAX_SWEEPS = 16
+COV_STATUS_NAMES = {COV_BAD_INPUT: "BAD_INPUT", COV_NO_FREE: "NO_FREE", COV_UNSEEN: "UNSEEN", COV_NO_DOF: "NO_DOF", COV_SINGULAR: "SINGULAR", COV_SWEEPS: "SWEEPS"}
 FLAG_RUNNING, ERR_INIT, ERR_STALL, ERR_MAXITERS, ERR_OUTPUT_FULL = -1, -11, -12, -13, -14
 
 BOUND_FIELDS = ["V_max", "V_min", "SOC_max", "SOC_min", "T_max", "c_s_n_max", "I_max", "I_min", "eta_plating_min",
@@ -108,7 +111,7 @@ assert RUN_INFO_DTYPE.itemsize == C.sizeof(RunInfo) and COUNTERS_DTYPE.itemsize 
 EXPORTS = ["plh_model_create", "plh_model_destroy", "plh_register_grid_library", "plh_n_states", "plh_n_diff", "plh_n_theta", "plh_theta_key",
            "plh_theta_default", "plh_lds_bytes", "plh_n_sections", "plh_section", "plh_jac_pattern", "plh_jac_alg_pattern", "plh_last_error", "plh_build_info", "plh_device_count", "plh_abi_layout",
            "plh_initial_guess", "plh_residual", "plh_jacobian", "plh_linear_solve", "plh_linear_solve_refined", "plh_residual_diff", "plh_residual_alg",
-           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_lm_step", "plh_lm_abi_layout", "plh_lsq_group", "plh_group_scatter", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
+           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_lm_step", "plh_lm_abi_layout", "plh_fit_cov", "plh_lsq_group", "plh_group_scatter", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
            "plh_comm_unique_id", "plh_comm_create", "plh_comm_destroy", "plh_comm_rank", "plh_comm_size", "plh_ensemble_run"]
 
 
@@ -178,6 +181,7 @@ def load(path=None):
     lib.plh_lsq_multi.argtypes = [vp, i, i, i, vp, vp, vp, i, C.POINTER(LsqChannel), i, i, vp, i, i, vp, vp, vp, vp, i, vp]
     lib.plh_lm_step.argtypes = [vp, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LMOpts), i, vp, i, vp]
     lib.plh_lm_abi_layout.argtypes = [vp, i]
+    lib.plh_fit_cov.argtypes = [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     lib.plh_lsq_group.argtypes = [vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     lib.plh_group_scatter.argtypes = [vp, i, i, vp, i, i, vp, vp, vp, i, vp]
     _cache[path] = lib

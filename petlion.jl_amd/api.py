@@ -1250,7 +1250,74 @@ class EnsembleFitResult:
     def __init__(self, keys):
         self.keys = list(keys)
         self.theta = self.cost = self.grad = self.JtJ = self.state = self.lam = self.n_accept = self.n_reject = self.history = self.group_off = None
+        self.theta_cur = self.n_data = None                              # [n, k]: the keys' values at the best point; [n] int32: the data of every problem (covariance)
         self.n_iter = 0
+        self._p = self._tf = self._lo = self._hi = self._stream = None   # what covariance() needs of the fit: the model, transform, the bounds as plh_lm_step took them, the launch stream
+
+    def covariance(self, absolute_sigma=False):
+        """Parameter covariances and identifiability at the best point of every problem (plh_fit_cov; csrc/plh_cov.h; include/petlion_hip.h states the definition), with the
+        fit's own transform and bounds: one row per cell, or per group for a grouped fit.  absolute_sigma=False: the residual variance is estimated, sigma2 =
+        2 cost / (n_data - n_free); True: the weights are taken as 1 / sigma of the data, sigma2 = 1 (scipy's absolute_sigma).  A fit in HBM stays there, queued on the fit's
+        launch stream.  Returns a FitCovariance."""
+        return fit_covariance(self._p, self.theta_cur, self.cost, self.grad, self.JtJ, n_data=None if absolute_sigma else self.n_data, transform=self._tf, lo=self._lo, hi=self._hi,
+                              stream=self._stream, keys=self.keys)
+
+
+class FitCovariance:
+    """fit_covariance's result, one row per problem; numpy arrays, or tensors in HBM.  sigma2 [n]: the residual variance; cov [n, k, k] and stderr [n, k] in the units of
+    theta (0 for a key held at a bound, NaN / +inf for a key the data do not see); corr [n, k, k]; eval [n, k] ascending and evec [n, k, k] (evec[:, j] is eigenvector j over
+    the keys): the eigen-decomposition of the normalised information matrix over the analysed keys -- the eigenvector of the smallest eigenvalue is the direction the data see
+    least; collinearity [n] = 1 / sqrt(eval[:, 0]) (Brun et al.); free [n]: bit i is set for a key that is not held; status [n]: 0, or bits cap.COV_* (names in
+    cap.COV_STATUS_NAMES; bits 8 .. 15: the keys the data do not see); keys."""
+
+    def __init__(self, keys):
+        self.keys = None if keys is None else list(keys)
+        self.sigma2 = self.cov = self.stderr = self.corr = self.eval = self.evec = self.collinearity = self.free = self.status = None
+
+
+def fit_covariance(p, theta_k, cost, grad, JtJ, *, n_data=None, transform=None, lo=None, hi=None, stream=None, keys=None):
+    """plh_fit_cov on the arrays a fit left behind: theta_k [n, k] (the keys' values), cost [n], grad [n, k], JtJ [n, k, k] -- fit_ensemble's result, or ens.lsq(...)'s arrays
+    (and .by_group's) with the keys' columns of Theta.  n_data [n] (int): the number of data of every problem, None: sigma2 = 1.  transform [k]: "log" / "linear" (or
+    cap.LM_LOG / cap.LM_LINEAR) per key, None: linear.  lo, hi: None, [k] (host) or [n, k] (where the inputs live), as fit_ensemble's bounds reach plh_lm_step.  numpy inputs
+    give numpy arrays; tensors in HBM give tensors in HBM, queued on `stream`.  Returns a FitCovariance."""
+    device = not isinstance(cost, np.ndarray)
+    n, k = grad.shape[0], grad.shape[1]
+    tf = np.zeros(k, np.int32) if transform is None else np.ascontiguousarray([{"linear": cap.LM_LINEAR, "log": cap.LM_LOG}.get(v, v) if isinstance(v, str) else int(v) for v in transform], dtype=np.int32)
+    if tf.shape != (k,):
+        raise ValueError("fit_covariance: transform must have one entry per key (%d)" % k)
+    if device:
+        import torch
+        dev = cost.device
+        conv = lambda a, dt=torch.float64: None if a is None else (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt).contiguous()
+        mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
+        kind, it = cap.PLH_DEVICE, torch.int32
+    else:
+        conv = lambda a, dt=np.float64: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        mk = lambda *shape, dt=np.float64: np.empty(shape, dt)
+        kind, it, stream = cap.PLH_HOST, np.int32, None
+    bdim = lambda b: 0 if b is None else (b.dim() if hasattr(b, "dim") else np.ndim(b))
+    per_cell = any(bdim(b) == 2 for b in (lo, hi))
+    if per_cell:                                                         # (one form for both sides: [n, k] where the inputs live)
+        full = lambda b, dflt: conv(np.full((n, k), dflt)) if b is None else (conv(b) if bdim(b) == 2 else conv(np.broadcast_to(np.asarray(b.cpu() if hasattr(b, "cpu") else b, dtype=np.float64), (n, k))))
+        lo_a, hi_a = full(lo, -np.inf), full(hi, np.inf)
+    else:                                                                # [k] on the host
+        lo_a, hi_a = (None if b is None else np.ascontiguousarray(b.cpu() if hasattr(b, "cpu") else b, dtype=np.float64) for b in (lo, hi))
+    ins = [conv(theta_k), conv(cost), conv(grad), conv(JtJ), conv(n_data, it)]
+    out = FitCovariance(keys)
+    out.sigma2, out.cov, out.stderr, out.corr, out.eval, out.evec, out.collinearity = mk(n), mk(n, k, k), mk(n, k), mk(n, k, k), mk(n, k), mk(n, k, k), mk(n)
+    out.free, out.status = mk(n, dt=it), mk(n, dt=it)
+    outs = [out.sigma2, out.cov, out.stderr, out.corr, out.eval, out.evec, out.collinearity, out.free, out.status]
+    ext = None
+    if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+        ext = torch.cuda.ExternalStream(int(stream), device=dev)         # (made or converted on torch's current stream, used on the launch stream: as in by_group)
+        ext.wait_stream(torch.cuda.current_stream(dev))
+    cap.check(p._lib, p._lib.plh_fit_cov(p._h, n, k, tf.ctypes.data, cap.ptr(ins[0]), cap.ptr(lo_a), cap.ptr(hi_a), 1 if per_cell else 0, cap.ptr(ins[1]), cap.ptr(ins[2]), cap.ptr(ins[3]),
+                                         cap.ptr(ins[4]), *[cap.ptr(v) for v in outs], kind, stream), "plh_fit_cov")
+    if ext is not None:
+        for v in ins + outs + [lo_a, hi_a]:
+            if hasattr(v, "record_stream"):
+                v.record_stream(ext)
+    return out
 
 
 LM_STATE_ARRAYS = ("theta_cur", "cost_cur", "grad_cur", "JtJ_cur", "lam", "pred", "state", "n_accept", "n_reject")
@@ -1336,6 +1403,27 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
         lo_a, hi_a = torch.as_tensor(blo).to(dev), torch.as_tensor(bhi).to(dev)
     else:
         lo_a, hi_a = np.ascontiguousarray(blo), np.ascontiguousarray(bhi)
+    # the number of data of every problem, for the residual variance of covariance(): the (channel, time) pairs whose weight is not 0 (a channel without weights: every
+    # time), summed over the members of a group; counted once, where the weights live
+    n_q = int(np.asarray(t.cpu() if hasattr(t, "cpu") else t).size)
+    xp = torch if device else np
+    n_data = mki((n,))
+    for d, w_ in ((V_data, weights), (I_data, I_weights), (T_avg_data, T_avg_weights)):
+        if d is None:
+            continue
+        if w_ is None:
+            n_data = n_data + n_q
+            continue
+        if device:
+            w_ = (w_ if isinstance(w_, torch.Tensor) else torch.as_tensor(np.asarray(w_, dtype=np.float64))).to(dev)
+        else:
+            w_ = np.asarray(w_, dtype=np.float64)
+        n_data = n_data + (w_ != 0).sum(-1).to(torch.int32) if device else n_data + (w_ != 0).sum(-1).astype(np.int32)
+    if off is not None:
+        cs = xp.cumsum(n_data, 0)
+        first_, last_ = (torch.as_tensor(off[:-1].astype(np.int64)).to(dev), torch.as_tensor(off[1:].astype(np.int64) - 1).to(dev)) if device else (off[:-1], off[1:] - 1)
+        n_data = cs[last_] - cs[first_] + n_data[first_]
+    n_data = n_data.to(torch.int32).contiguous() if device else np.ascontiguousarray(n_data, dtype=np.int32)
     st = dict(theta_cur=mk((nf, k)), cost_cur=mk((nf,)), grad_cur=mk((nf, k)), JtJ_cur=mk((nf, k, k)), lam=mk((nf,)), pred=mk((nf,)), state=mki((nf,)), n_accept=mki((nf,)), n_reject=mki((nf,)))
     n_running = mki((1,))
     LTheta, gfit = Theta, None                                           # the matrix plh_lm_step works on: one row per problem
@@ -1348,7 +1436,7 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
     if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
         ext = torch.cuda.ExternalStream(int(stream), device=dev)         # (made on torch's current stream, used on the launch stream: as in _integrate)
         ext.wait_stream(torch.cuda.current_stream(dev))
-        for v in [Theta, n_running, lo_a, hi_a] + list(st.values()) + ([] if off is None else [LTheta, gfit.cost, gfit.grad, gfit.JtJ, gfit.status]):
+        for v in [Theta, n_running, lo_a, hi_a, n_data] + list(st.values()) + ([] if off is None else [LTheta, gfit.cost, gfit.grad, gfit.JtJ, gfit.status]):
             if hasattr(v, "record_stream"):
                 v.record_stream(ext)
     res = EnsembleFitResult(keys)
@@ -1399,6 +1487,8 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
         iteration(cap.LM_LAST)
     res.theta, res.cost, res.grad, res.JtJ = Theta, st["cost_cur"], st["grad_cur"], st["JtJ_cur"]
     res.state, res.lam, res.n_accept, res.n_reject = st["state"], st["lam"], st["n_accept"], st["n_reject"]
+    res.theta_cur, res.n_data = st["theta_cur"], n_data
+    res._p, res._tf, res._lo, res._hi, res._stream = p, tf, lo_a, hi_a, stream
     return res
 
 

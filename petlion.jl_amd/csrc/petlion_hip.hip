@@ -37,6 +37,7 @@
 #include "plh_resample.h"
 #include "plh_lsq.h"
 #include "plh_lm.h"
+#include "plh_cov.h"
 #include "plh_group.h"
 
 using namespace pl;
@@ -1418,6 +1419,52 @@ int plh_lm_step(plh_model_t m, int n, int n_theta, double* theta, int n_keys, co
   s.back(theta, A.theta, nth); s.back(theta_cur, A.theta_cur, nk); s.back(cost_cur, A.cost_cur, nn); s.back(grad_cur, A.grad_cur, nk); s.back(JtJ_cur, A.JtJ_cur, nkk);
   s.back(lambda, A.lambda, nn); s.back(pred, A.pred, nn); s.back(state, A.state, nn); s.back(n_accept, A.n_accept, nn); s.back(n_reject, A.n_reject, nn);
   s.back(n_running, d_count, 1);
+  CHECK_STAGE(s);
+  return 0;
+}
+
+// ---- plh_fit_cov: covariances and identifiability of the fitted problems (kernel: plh_cov.h).  transform and shared bounds are host memory; the shared bounds' device copy is
+// the one plh_lm_step remembers per stream: after a fit with the same bounds nothing is uploaded and nothing synchronises.  The inputs are only read ----
+int plh_fit_cov(plh_model_t m, int n, int n_keys, const int* transform, const double* theta_k, const double* lo, const double* hi, int bounds_per_cell,
+                const double* cost, const double* grad, const double* JtJ, const int* n_data, double* sigma2, double* cov, double* stderr_, double* corr,
+                double* eval, double* evec, double* collinearity, int* free_mask, int* status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1) return fail(PLH_E_ARG, "plh_fit_cov: n must be >= 1");
+  if (n_keys < 1 || n_keys > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_fit_cov: n_keys must be 1 .. PLH_LSQ_MAX_SENS (8)");
+  if (bounds_per_cell != 0 && bounds_per_cell != 1) return fail(PLH_E_ARG, "plh_fit_cov: bounds_per_cell must be 0 or 1");
+  if (!transform || !theta_k || !cost || !grad || !JtJ || !sigma2 || !cov || !stderr_ || !corr || !eval || !evec || !collinearity || !free_mask || !status)
+    return fail(PLH_E_ARG, "plh_fit_cov: null array (only lo, hi and n_data may be NULL)");
+  plcov::Args A;
+  A.logmask = 0;
+  std::vector<double> shared(2 * (size_t)n_keys);                    // lo, then hi
+  for (int i = 0; i < n_keys; i++) {
+    if (transform[i] != PLH_LM_LINEAR && transform[i] != PLH_LM_LOG) return fail(PLH_E_ARG, "plh_fit_cov: transform must be PLH_LM_LINEAR or PLH_LM_LOG");
+    if (transform[i] == PLH_LM_LOG) A.logmask |= 1u << i;
+    if (!bounds_per_cell) {
+      shared[i] = lo ? lo[i] : -HUGE_VAL; shared[n_keys + i] = hi ? hi[i] : HUGE_VAL;
+      if (!(shared[i] <= shared[n_keys + i])) return fail(PLH_E_ARG, "plh_fit_cov: shared bounds with lo > hi (or a NaN)");
+    }
+  }
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  const size_t nn = (size_t)n, nk = nn * n_keys, nkk = nk * n_keys;
+  A.n = n; A.n_keys = n_keys; A.bstride = bounds_per_cell ? n_keys : 0;
+  A.theta = s.in(theta_k, nk);
+  A.lo = bounds_per_cell ? s.in(lo, nk) : nullptr; A.hi = bounds_per_cell ? s.in(hi, nk) : nullptr;
+  if (!bounds_per_cell) {
+    const double* d_shared = nullptr;
+    if (int rc = s.cx->lm_bounds.get(s.cx->st, shared, &d_shared)) return rc;
+    A.lo = d_shared; A.hi = d_shared + n_keys;
+  }
+  A.cost = s.in(cost, nn); A.grad = s.in(grad, nk); A.JtJ = s.in(JtJ, nkk); A.n_data = s.in(n_data, nn);
+  A.sigma2 = s.buf(sigma2, nn, false); A.cov = s.buf(cov, nkk, false); A.se = s.buf(stderr_, nk, false); A.corr = s.buf(corr, nkk, false);
+  A.eval = s.buf(eval, nk, false); A.evec = s.buf(evec, nkk, false); A.coll = s.buf(collinearity, nn, false);
+  A.free_mask = s.buf(free_mask, nn, false); A.status = s.buf(status, nn, false);
+  CHECK_STAGE(s);
+  plcov::launch(s.st, A);
+  FINISH(s);
+  s.back(sigma2, A.sigma2, nn); s.back(cov, A.cov, nkk); s.back(stderr_, A.se, nk); s.back(corr, A.corr, nkk);
+  s.back(eval, A.eval, nk); s.back(evec, A.evec, nkk); s.back(collinearity, A.coll, nn); s.back(free_mask, A.free_mask, nn); s.back(status, A.status, nn);
   CHECK_STAGE(s);
   return 0;
 }

@@ -19,7 +19,13 @@ Shape: the C4 shard (8192 jittered cells, 1C discharge), the seven sweep paramet
   fits               the seven keys from starts at 2^(+-0.25) of the truth, max_iter as above: 2048 groups of 4 members at 0.5C / 1C / 2C / 3C against 8192 single 1C cells,
                      the same number of data per problem (200: the groups' members have 50 each) with 2 mV of noise; the final states, cond of the final JtJ in log
                      parameters, and how far the best point is from the truth
-  bench_c2_same_box  with --c2-line FILE: the line `bench.py --gpus 1` printed on the same box (the integrator is untouched by the grouping)"""
+  bench_c2_same_box  with --c2-line FILE: the line `bench.py --gpus 1` printed on the same box (the integrator is untouched by the grouping)
+
+  python tools/lm_bench.py --cov [--out profiles/fit_cov.json]               covariances and identifiability of the fitted problems (plh_fit_cov)
+  fit_cov            one plh_fit_cov on the state plh_lm_step (FIRST) left in HBM for the C4-shard shape (8192 problems, seven LOG keys, n_data = 200) and on the same fit summed
+                     into 2048 groups of 4 (n_data = 800): HIP events around the call, median of --reps after a warm-up; alternating in the same process with the torch
+                     composition of the same numbers (scaling, normalisation, linalg.cholesky_ex, cholesky_inverse, linalg.eigh on the normalised matrix: no bounds, no active
+                     set, no unseen keys, no status); both as a share of the sensitivity integration; bench_c2_same_box as above"""
 import argparse
 import json
 import os
@@ -41,12 +47,17 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--max-iter", type=int, default=12)
     ap.add_argument("--groups", action="store_true", help="measure the grouped calls and the grouped fit instead (default --out: profiles/lm_groups.json)")
-    ap.add_argument("--c2-line", default=None, help="--groups: a file whose last line is the JSON line `bench.py --gpus 1` printed on the same box; kept in the record as bench_c2_same_box")
+    ap.add_argument("--cov", action="store_true", help="measure plh_fit_cov instead (default --out: profiles/fit_cov.json)")
+    ap.add_argument("--c2-line", default=None, help="--groups / --cov: a file whose last line is the JSON line `bench.py --gpus 1` printed on the same box; kept in the record as bench_c2_same_box")
     a = ap.parse_args()
     if a.groups:
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "lm_groups.json")
         return main_groups(a)
+    if a.cov:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "fit_cov.json")
+        return main_cov(a)
     import torch
     assert torch.cuda.is_available(), "tools/lm_bench.py measures on a GPU"
     import pkgload
@@ -243,6 +254,80 @@ def main_groups(a):
 
     fits = {"groups_of_4": run(rates, n // 4, True), "single_1C_cells": run([1.0], n, False)}
     rec = {"cells": n, "n_q": n_q, "keys": keys, "transform": "log", "max_iter": a.max_iter, "sens_integration": spread(ms_s), "group_calls": calls, "fits": fits,
+           "build_info": p._lib.plh_build_info().decode()}
+    if a.c2_line:                                                               # the integrator of the same binary on the same box
+        b = json.loads([line for line in open(a.c2_line) if line.startswith('{"metric"')][-1])
+        rec["bench_c2_same_box"] = dict({x: b[x] for x in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step")}, kernel_ms_avg=b["roofline"]["kernel_ms_avg"])
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(rec, open(a.out, "w"), indent=1)
+    print(json.dumps(rec))
+
+
+def main_cov(a):
+    import torch
+    assert torch.cuda.is_available(), "tools/lm_bench.py measures on a GPU"
+    import pkgload
+    pkg = pkgload.load()
+    cap = pkg._capi
+    p = pkg.petlion(pkg.LCO)
+    n, n_q = a.cells, a.points
+    keys = [k for k in pkg.configs.SWEEP_KEYS if k in p.θ_keys]
+    k = len(keys)
+    cols_t = torch.from_numpy(np.asarray([p.θ_keys.index(x) for x in keys], dtype=np.int64)).cuda()
+    rng = np.random.default_rng(0)
+    cfg = pkg.configs.c4(p, n)
+    Th = torch.from_numpy(cfg["theta"]).cuda()
+    sim = lambda: pkg.simulate_ensemble(p, Th, cfg["protocol"], SOC=cfg["SOC"], device=True, max_points=cfg["max_points"], sens=keys)
+    ens = sim()
+    torch.cuda.synchronize()
+    tq = np.linspace(0.0, float(ens.run_info["t_end"][:, -1].min()), n_q)
+    data = ens(tq, fields="V").V[0] + torch.from_numpy(2e-3 * rng.standard_normal(n_q)).cuda()
+    w = torch.full((n_q,), 1 / 2e-3, dtype=torch.float64, device="cuda")
+    fit = ens.lsq(tq, data, weights=w)
+    ms_s = []
+    for _ in range(3):
+        e = sim(); torch.cuda.synchronize(); ms_s.append(float(e.kernel_ms))
+    theta_k = Th[:, cols_t].contiguous()
+    tf = ["log"] * k
+    names = cap.COV_STATUS_NAMES
+
+    def measure(th_k, f, n_data):
+        nd = torch.full((th_k.shape[0],), n_data, dtype=torch.int32, device="cuda")
+        ours = lambda: pkg.fit_covariance(p, th_k, f.cost, f.grad, f.JtJ, n_data=nd, transform=tf, keys=keys)
+
+        def torch_composition():
+            s = th_k[:, :, None] * th_k[:, None, :]
+            Hs = f.JtJ * s
+            r = torch.sqrt(torch.diagonal(Hs, dim1=1, dim2=2))
+            rr = r[:, :, None] * r[:, None, :]
+            C = Hs / rr
+            L, _ = torch.linalg.cholesky_ex(C)
+            P = torch.cholesky_inverse(L)
+            d = torch.sqrt(torch.diagonal(P, dim1=1, dim2=2))
+            sigma2 = 2.0 * f.cost / (n_data - k)
+            cov = s * (P * sigma2[:, None, None] / rr)
+            ev, V = torch.linalg.eigh(C)
+            return sigma2, cov, torch.sqrt(torch.diagonal(cov, dim1=1, dim2=2)), P / (d[:, :, None] * d[:, None, :]), ev, V, 1.0 / torch.sqrt(ev[:, 0])
+
+        cv, tc = ours(), torch_composition(); torch.cuda.synchronize()           # warm-up of both
+        ms_k, ms_t = [], []
+        for _ in range(a.reps):
+            ms_k.append(timed(ours)[0])
+            ms_t.append(timed(torch_composition)[0])
+        st, coll, ev = cv.status.cpu().numpy(), cv.collinearity.cpu().numpy(), cv.eval.cpu().numpy()
+        plain = st == 0
+        q = lambda x: {"p10": float(np.nanpercentile(x, 10)), "median": float(np.nanmedian(x)), "p90": float(np.nanpercentile(x, 90))}
+        d_ev = float(np.abs(ev[plain] - tc[4].cpu().numpy()[plain]).max()) if plain.any() else None
+        return {"problems": int(th_k.shape[0]), "n_data": n_data, "plh_fit_cov": spread(ms_k), "torch_composition": spread(ms_t), "ours_over_torch_composition": float(np.median(ms_k) / np.median(ms_t)),
+                "ours_over_sens_integration": float(np.median(ms_k) / np.median(ms_s)), "torch_composition_over_sens_integration": float(np.median(ms_t) / np.median(ms_s)),
+                "status_counts": {nm: int(((st & b) != 0).sum()) for b, nm in names.items()}, "status_0": int(plain.sum()), "collinearity": q(coll[np.isfinite(coll)]),
+                "max_abs_eval_difference_to_eigh_status_0": d_ev}
+
+    labels = np.repeat(np.arange(n // 4), 4)
+    gf = fit.by_group(labels)
+    first = torch.from_numpy(np.arange(0, n, 4)).cuda()
+    rec = {"cells": n, "n_q": n_q, "keys": keys, "transform": "log", "sens_integration": spread(ms_s),
+           "fit_cov": {"%d_problems" % n: measure(theta_k, fit, n_q), "%d_groups_of_4" % (n // 4): measure(theta_k[first].contiguous(), gf, 4 * n_q)},
            "build_info": p._lib.plh_build_info().decode()}
     if a.c2_line:                                                               # the integrator of the same binary on the same box
         b = json.loads([line for line in open(a.c2_line) if line.startswith('{"metric"')][-1])
