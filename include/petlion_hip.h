@@ -621,6 +621,43 @@ int plh_fit_cov(plh_model_t m, int n, int n_keys, const int* transform /* [k], H
                 double* eval /* [n][k] */, double* evec /* [n][k][k] */, double* collinearity /* [n] */,
                 int* free_mask /* [n] */, int* status /* [n] */, int ptr_kind, void* stream);
 
+/* ---- prediction bands: every cell's measured curves and their sensitivities at query times of the caller's choosing, and the variance of the predicted curve under the
+ * covariance of the fitted keys.  It answers "how well is the curve known?" after plh_fit_cov answered "how well are the parameters known?", from arrays that are already in
+ * device memory after a fit: the per-point curves, their per-point sensitivities (plh_integrate_sens_out) and cov[n][k][k].
+ * Channel c is a per-point curve and the rows of its per-point sensitivities, as in plh_lsq_multi.  S_c and S_ck are exactly plh_resample's functions of channel c's curve
+ * and of row k of its dcurve: the same run-assignment rule, the same not-a-knot cubic with the same n = 3 / 2 / 1 fall-backs, the same clamping (extrapolate = 0) or
+ * continuation (1).  With k = n_sens (1 .. PLH_LSQ_MAX_SENS; a call without sensitivities is plh_resample) and query times tq_q:
+ *   ch[c].pred[cell][q]     = S_c(tq_q)
+ *   ch[c].dpred[cell][i][q] = S_ci(tq_q)       the derivative of the resampled curve AT FIXED KNOTS, as everywhere in this library
+ *   ch[c].var[cell][q]      = sum_i s_i v_i (i ascending), with s_i = S_ci(tq_q) and v_i = sum_j M_ij s_j (j ascending)
+ * M is the upper triangle (row <= column) of the cell's covariance, mirrored.  This is the delta-method variance of the predicted curve, in the units of the curve squared.
+ * cov is in theta units, as plh_fit_cov writes it (its delta method for PLH_LM_LOG keys is already inside).  var is stored as computed: it is not clamped and no square
+ * root is taken, so a tiny negative value from cancellation stays visible.  It is the variance of the curve, not of a new observation (the caller adds sigma^2 for that).
+ * Every output pointer of a channel may be NULL (not written), but not all three; a query at a saved time returns the saved bits in pred and dpred.
+ * NaN flows through the arithmetic.  A held key has 0 rows and columns in cov and contributes nothing.  A problem with an unseen key (NaN rows) or a failed covariance
+ * gets var = NaN and keeps pred and dpred.  A NaN in one channel's dcurve reaches that channel's dpred and var of that cell only.  A NaN tq_q gives NaN at q in every output.
+ * Which covariance a cell takes.  group_off == NULL: cov[cell] (cov is [n_cells][k][k]; n_groups is ignored).  Otherwise cov[g] of the group g that owns the cell (cov is
+ * [n_groups][k][k]); group_off[n_groups + 1] is HOST memory and follows plh_lsq_group's rules, and its device copy is the one plh_lsq_group remembers per stream: after a
+ * grouped fit nothing is uploaded and nothing synchronises.
+ * Cells that cannot be resampled (plh_resample's rule, status[cell] = 1): every output row of the cell is NaN, none of its points is read, other cells do not notice.
+ * ch[n_ch] itself and tq[n_q] are HOST memory for every ptr_kind; the pointers in ch and every other array follow ptr_kind.  PLH_HOST blocks, PLH_DEVICE is asynchronous
+ * on `stream`.  The slopes of the n_ch (1 + k) columns live in plh_resample's per-stream workspace, bounded the same way (PLH_RESAMPLE_WS_BYTES).  Every output is computed
+ * by one lane in one order: the bits do not depend on the chunking or the pointer kind, and a channel's outputs do not depend on what else is in the call.
+ * PLH_E_ARG, nothing written, nothing clamped: n_cells, n_runs, max_pts or n_q < 1; n_sens outside 1 .. PLH_LSQ_MAX_SENS; n_ch outside 1 .. PLH_LSQ_MAX_CHANNELS;
+ * extrapolate not 0 / 1; a NULL among t, n_pts, run_info, ch, tq; a NULL curve or dcurve in a channel; a channel whose pred, dpred and var are all NULL; a var without cov;
+ * with a group_off: plh_lsq_group's cases (n_groups < 1 or > n_cells, offsets that do not start at 0, do not end at n_cells or are not strictly ascending). */
+typedef struct {
+  const double* curve;   /* [n_cells][max_pts]            (V, I or T_avg as plh_integrate_sens_out wrote it) */
+  const double* dcurve;  /* [n_cells][n_sens][max_pts] */
+  double* pred;          /* [n_cells][n_q]          or NULL */
+  double* dpred;         /* [n_cells][n_sens][n_q]  or NULL */
+  double* var;           /* [n_cells][n_q]          or NULL; non-NULL needs cov */
+} plh_predict_channel;
+int plh_predict(plh_model_t m, int n_cells, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info,
+                int n_ch, const plh_predict_channel* ch /* HOST */, int n_sens, int n_q, const double* tq /* HOST */, int extrapolate,
+                const double* cov /* [n_prob][n_sens][n_sens] or NULL */, int n_groups, const int* group_off /* [n_groups + 1], HOST, or NULL */,
+                int* status /* [n_cells] or NULL */, int ptr_kind, void* stream);
+
 /* timing of the last plh_integrate kernel on its stream, measured with HIP events (ms); <0 if unavailable */
 double plh_last_kernel_ms(plh_model_t m);
 

@@ -89,6 +89,10 @@ class LsqChannel(C.Structure):             # plh_lsq_channel
     _fields_ = [("curve", C.c_void_p), ("dcurve", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p), ("resid", C.c_void_p)]
 
 
+class PredictChannel(C.Structure):         # plh_predict_channel
+    _fields_ = [("curve", C.c_void_p), ("dcurve", C.c_void_p), ("pred", C.c_void_p), ("dpred", C.c_void_p), ("var", C.c_void_p)]
+
+
 LM_OPT_FIELDS = ["lambda0", "lambda_up", "lambda_down", "lambda_min", "lambda_max", "eta", "ftol", "xtol", "gtol", "diag_floor"]
 LM_OPT_DEFAULTS = dict(zip(LM_OPT_FIELDS, (1e-3, 3.0, 1.0 / 3.0, 1e-12, 1e12, 1e-4, 1e-10, 1e-8, 1e-8, 1e-12)))      # PLH_LM_OPTS_DEFAULT
 
@@ -111,7 +115,7 @@ assert RUN_INFO_DTYPE.itemsize == C.sizeof(RunInfo) and COUNTERS_DTYPE.itemsize 
 EXPORTS = ["plh_model_create", "plh_model_destroy", "plh_register_grid_library", "plh_n_states", "plh_n_diff", "plh_n_theta", "plh_theta_key",
            "plh_theta_default", "plh_lds_bytes", "plh_n_sections", "plh_section", "plh_jac_pattern", "plh_jac_alg_pattern", "plh_last_error", "plh_build_info", "plh_device_count", "plh_abi_layout",
            "plh_initial_guess", "plh_residual", "plh_jacobian", "plh_linear_solve", "plh_linear_solve_refined", "plh_residual_diff", "plh_residual_alg",
-           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_lm_step", "plh_lm_abi_layout", "plh_fit_cov", "plh_lsq_group", "plh_group_scatter", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
+           "plh_jacobian_alg", "plh_init_consistent", "plh_integrate", "plh_integrate_sens", "plh_integrate_sens_out", "plh_model_attach_closure_library", "plh_last_integrate_compiled", "plh_closure_digest", "plh_resample", "plh_lsq", "plh_lsq_multi", "plh_lm_step", "plh_lm_abi_layout", "plh_fit_cov", "plh_predict", "plh_lsq_group", "plh_group_scatter", "plh_last_kernel_ms", "plh_host_alloc", "plh_host_free", "plh_synchronize",
            "plh_comm_unique_id", "plh_comm_create", "plh_comm_destroy", "plh_comm_rank", "plh_comm_size", "plh_ensemble_run"]
 
 
@@ -182,6 +186,7 @@ def load(path=None):
     lib.plh_lm_step.argtypes = [vp, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(LMOpts), i, vp, i, vp]
     lib.plh_lm_abi_layout.argtypes = [vp, i]
     lib.plh_fit_cov.argtypes = [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
+    lib.plh_predict.argtypes = [vp, i, i, i, vp, vp, vp, i, C.POINTER(PredictChannel), i, i, vp, i, vp, i, vp, vp, i, vp]
     lib.plh_lsq_group.argtypes = [vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
     lib.plh_group_scatter.argtypes = [vp, i, i, vp, i, i, vp, vp, vp, i, vp]
     _cache[path] = lib

@@ -968,6 +968,33 @@ def _lsq_group(p, off, fit, out, stream):
                                            cap.ptr(out.cost), cap.ptr(out.grad), cap.ptr(out.JtJ), cap.ptr(out.status), kind, stream if kind == cap.PLH_DEVICE else None), "plh_lsq_group")
 
 
+class EnsemblePrediction:
+    """ens.predict(t, cov): an ensemble's measured curves, their sensitivities and their prediction bands on one time grid (EnsembleSolution.predict).  t [n_q]; keys; channels:
+    the names of the channels evaluated; per channel c of them V / I / T_avg [cell, n_q] (the resampled curve), dV_dtheta / dI_dtheta / dT_avg_dtheta [cell, k, n_q] (the
+    resampled sensitivities), V_var / I_var / T_avg_var [cell, n_q] (the delta-method variance s' cov s of the curve, as computed: a tiny negative value from cancellation
+    stays visible) and V_sd / I_sd / T_avg_sd = sqrt(max(var, 0)) -- var and sd are None without a covariance, and everything of a channel that was not evaluated is None;
+    status [cell] (1: the cell failed or was cut at max_points -- its rows are NaN).  The band of the CURVE: a prediction interval for a new observation adds the
+    measurement's sigma^2 to var."""
+
+    def __init__(self, t, keys, channels):
+        self.t, self.keys, self.channels = t, list(keys), list(channels)
+        self.status = None
+        for c in SENS_CHANNELS:
+            for nm in (c, SENS_CHANNELS[c], c + "_var", c + "_sd"):
+                setattr(self, nm, None)
+
+
+def _group_offsets_or_labels(groups, n_cells):
+    """the offsets [n_groups + 1] of `groups`, given as labels [n_cells] (group_offsets) or as the offsets themselves (an integer array that ends at n_cells: no array of
+    labels does)"""
+    g = np.asarray(groups.cpu() if hasattr(groups, "cpu") else groups)
+    if g.ndim == 1 and g.size >= 2 and np.issubdtype(g.dtype, np.integer) and int(g[-1]) == n_cells:
+        if g[0] != 0 or (np.diff(g.astype(np.int64)) < 1).any():
+            raise ValueError("groups: offsets must start at 0, end at n_cells and be strictly ascending (every group has a member)")
+        return np.ascontiguousarray(g, dtype=np.int32)
+    return group_offsets(g, n_cells)
+
+
 class EnsembleSolution:
     """Per-cell results of an ensemble run (arrays indexed [cell, point]); sol[i] gives a single-cell Solution."""
 
@@ -1151,6 +1178,90 @@ class EnsembleSolution:
                     v.record_stream(ext)
         return out
 
+    def predict(self, t, cov=None, groups=None, channels=None, interp_bc="interpolate"):
+        """Prediction bands on the device (plh_predict; csrc/plh_predict.h; include/petlion_hip.h states the definition): the measured curves of an ensemble run with
+        sens=[keys] and the rows of their sensitivities on the time grid t [n_q] -- the functions ens(t) and ens.lsq evaluate -- and, with a covariance of the keys, the
+        delta-method variance s' cov s of every curve at every time.  channels: of "V", "I", "T_avg"; default: every channel whose sensitivities the ensemble carries
+        (simulate_ensemble(sens_outputs=...)).  cov: None (no variance), a FitCovariance (fit_covariance, res.covariance()) or an [n_prob, k, k] array / tensor in the units
+        of theta; n_prob = n_cells, or with groups (labels [n_cells] as fit_ensemble takes them, or offsets [n_groups + 1]) n_groups: every member of a group takes its
+        group's matrix.  interp_bc as ens(t).  A device=True ensemble gets tensors in HBM, queued on the launch stream; a host ensemble numpy arrays.  Returns an
+        EnsemblePrediction."""
+        if interp_bc not in ("interpolate", "extrapolate"):
+            raise ValueError("Invalid interp_bc method.")
+        tq = np.ascontiguousarray(np.atleast_1d(np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=np.float64)))
+        if tq.ndim != 1 or tq.size < 1:
+            raise ValueError("t must be a time or a 1-D array of times")
+        n, mp = self.t.shape
+        ns = len(self.keys)
+        if ns < 1:
+            raise ValueError("ens.predict needs an ensemble run with sens=[keys]; without sensitivities ens(t) resamples the curves")
+        if ns > cap.LSQ_MAX_SENS:
+            raise ValueError("ens.predict takes at most %d sens keys per call (this ensemble has %d)" % (cap.LSQ_MAX_SENS, ns))
+        have = [c for c in SENS_CHANNELS if getattr(self, c, None) is not None and getattr(self, SENS_CHANNELS[c], None) is not None]
+        names = have if channels is None else [channels] if isinstance(channels, str) else list(channels)
+        for c in names:
+            if c not in SENS_CHANNELS:
+                raise ValueError("channels: %r is not one of %s" % (c, ", ".join(SENS_CHANNELS)))
+            if c not in have:
+                raise ValueError("this ensemble was run without the sensitivities of %s; ask for them with simulate_ensemble(..., sens_outputs=(..., %r))" % (c, c))
+        names = [c for c in SENS_CHANNELS if c in names]
+        if not names:
+            raise ValueError("ens.predict: this ensemble carries no channel with its sensitivities (simulate_ensemble(sens=[keys], sens_outputs=...))")
+        if groups is not None and cov is None:
+            raise ValueError("ens.predict: groups say which covariance a cell takes; give cov")
+        off = None if groups is None else _group_offsets_or_labels(groups, n)
+        n_prob = n if off is None else len(off) - 1
+        cv = cov.cov if isinstance(cov, FitCovariance) else cov
+        if cv is not None and tuple(cv.shape) != (n_prob, ns, ns):
+            raise ValueError("cov must be [%s, k, k] = [%d, %d, %d], not %s" % ("n_cells" if off is None else "n_groups", n_prob, ns, ns, list(cv.shape)))
+        device = not isinstance(self.t, np.ndarray)
+        if device:
+            import torch
+            dev = self.t.device
+            conv = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
+            mk = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)
+            kind, stream, rinfo = cap.PLH_DEVICE, self._stream, self._run_info_raw
+        else:
+            conv = lambda a: np.ascontiguousarray(a.cpu() if hasattr(a, "cpu") else a, dtype=np.float64)
+            mk = lambda *shape, dt=np.float64: np.empty(shape, dt)
+            kind, stream, rinfo = cap.PLH_HOST, None, np.ascontiguousarray(self.run_info)
+        cv = None if cv is None else conv(cv)
+        ext = None
+        if device and stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)      # (made or converted on torch's current stream, used on the launch stream: as in fit_covariance)
+            ext.wait_stream(torch.cuda.current_stream(dev))
+        out = EnsemblePrediction(tq, self.keys, names)
+        out.status = mk(n, dt=torch.int32 if device else np.int32)
+        ch = (cap.PredictChannel * len(names))()
+        for q, c in enumerate(names):
+            setattr(out, c, mk(n, tq.size))
+            setattr(out, SENS_CHANNELS[c], mk(n, ns, tq.size))
+            if cv is not None:
+                setattr(out, c + "_var", mk(n, tq.size))
+            ch[q] = cap.PredictChannel(cap.ptr(getattr(self, c)), cap.ptr(getattr(self, SENS_CHANNELS[c])), cap.ptr(getattr(out, c)), cap.ptr(getattr(out, SENS_CHANNELS[c])),
+                                       cap.ptr(getattr(out, c + "_var")))
+        lib, h = self.p._lib, self.p._h
+        cap.check(lib, lib.plh_predict(h, n, len(self.run_names), mp, cap.ptr(self.t), cap.ptr(self.n_pts), cap.ptr(rinfo), len(names), ch, ns, tq.size, tq.ctypes.data,
+                                       1 if interp_bc == "extrapolate" else 0, cap.ptr(cv), 0 if off is None else len(off) - 1, None if off is None else off.ctypes.data,
+                                       cap.ptr(out.status), kind, stream), "plh_predict")
+        if cv is not None:                                               # sd = sqrt(max(var, 0)) (NaN stays NaN), behind the kernel on its stream
+            for c in names:
+                var = getattr(out, c + "_var")
+                if not device:
+                    sd = np.sqrt(np.maximum(var, 0.0))
+                elif ext is None:
+                    sd = torch.sqrt(torch.clamp(var, min=0.0))
+                else:
+                    with torch.cuda.stream(ext):
+                        sd = torch.sqrt(torch.clamp(var, min=0.0))
+                    sd.record_stream(torch.cuda.current_stream(dev))
+                setattr(out, c + "_sd", sd)
+        if ext is not None:
+            for v in [cv, out.status] + [getattr(out, nm) for c in names for nm in (c, SENS_CHANNELS[c], c + "_var")]:
+                if v is not None:
+                    v.record_stream(ext)
+        return out
+
     def __getitem__(self, i):
         host = lambda x: (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)).copy()      # device=True results are torch tensors in HBM
         s = Solution()
@@ -1253,6 +1364,7 @@ class EnsembleFitResult:
         self.theta_cur = self.n_data = None                              # [n, k]: the keys' values at the best point; [n] int32: the data of every problem (covariance)
         self.n_iter = 0
         self._p = self._tf = self._lo = self._hi = self._stream = None   # what covariance() needs of the fit: the model, transform, the bounds as plh_lm_step took them, the launch stream
+        self._protocol = self._SOC = self._opts = self._max_points = self._device = self._sens_outputs = self._interp_bc = None      # what predict() needs to integrate once more
 
     def covariance(self, absolute_sigma=False):
         """Parameter covariances and identifiability at the best point of every problem (plh_fit_cov; csrc/plh_cov.h; include/petlion_hip.h states the definition), with the
@@ -1261,6 +1373,15 @@ class EnsembleFitResult:
         launch stream.  Returns a FitCovariance."""
         return fit_covariance(self._p, self.theta_cur, self.cost, self.grad, self.JtJ, n_data=None if absolute_sigma else self.n_data, transform=self._tf, lo=self._lo, hi=self._hi,
                               stream=self._stream, keys=self.keys)
+
+    def predict(self, t, absolute_sigma=False, channels=None):
+        """Prediction bands of the fitted curves at the times t [n_q]: one sensitivity integration at the best point self.theta (the last integration of the fit was that of
+        the last TRIAL, not of the best point), then ens.predict(t, self.covariance(absolute_sigma)) with the fit's grouping, channels and interp_bc.  channels: of the
+        channels the fit had data of (default: all of them).  A fit in HBM stays there.  Returns an EnsemblePrediction; every member of a group is banded with its group's
+        covariance."""
+        ens = simulate_ensemble(self._p, self.theta, self._protocol, SOC=self._SOC, opts=self._opts, device=self._device, stream=self._stream, max_points=self._max_points,
+                                YP=False, sens=self.keys, sens_outputs=self._sens_outputs)
+        return ens.predict(t, cov=self.covariance(absolute_sigma), groups=self.group_off, channels=channels, interp_bc=self._interp_bc)
 
 
 class FitCovariance:
@@ -1489,6 +1610,7 @@ def fit_ensemble(p, Theta0, protocol, keys, t, V_data=None, weights=None, I_data
     res.state, res.lam, res.n_accept, res.n_reject = st["state"], st["lam"], st["n_accept"], st["n_reject"]
     res.theta_cur, res.n_data = st["theta_cur"], n_data
     res._p, res._tf, res._lo, res._hi, res._stream = p, tf, lo_a, hi_a, stream
+    res._protocol, res._SOC, res._opts, res._max_points, res._device, res._sens_outputs, res._interp_bc = protocol, SOC, opts, max_points, device, tuple(given), interp_bc
     return res
 
 

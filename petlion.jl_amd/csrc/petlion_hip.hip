@@ -36,6 +36,7 @@
 
 #include "plh_resample.h"
 #include "plh_lsq.h"
+#include "plh_predict.h"
 #include "plh_lm.h"
 #include "plh_cov.h"
 #include "plh_group.h"
@@ -1352,6 +1353,56 @@ int plh_lsq_multi(plh_model_t m, int n, int n_runs, int max_pts, const double* t
   FINISH(s);
   s.back(cost, A.cost, (size_t)n); s.back(grad, A.grad, n * ns); s.back(JtJ, A.JtJ, n * ns * ns);
   for (int c = 0; c < n_ch; c++) s.back(ch[c].resid, A.ch[c].resid, (size_t)n * n_q);
+  s.back(status, a.status, (size_t)n);
+  CHECK_STAGE(s);
+  return 0;
+}
+
+// ---- plh_predict: every channel's curve and sensitivities at the query times, and the variance of the curve under the covariance of the keys (kernel: plh_predict.h; the
+// slopes share plh_resample's workspace and its chunking like plh_lsq_multi's; the offsets' device copy is the one plh_lsq_group remembers per stream) ----
+static int check_groups(const char* who, int n, int n_groups, const int* group_off);
+int plh_predict(plh_model_t m, int n, int n_runs, int max_pts, const double* t, const int* n_pts, const plh_run_info* run_info, int n_ch, const plh_predict_channel* ch,
+                int n_sens, int n_q, const double* tq, int extrapolate, const double* cov, int n_groups, const int* group_off, int* status, int kind, void* stream) {
+  CHECK_MODEL(m); CHECK_KIND(kind);
+  if (n < 1 || n_runs < 1 || max_pts < 1 || n_q < 1) return fail(PLH_E_ARG, "plh_predict: n_cells, n_runs, max_pts and n_q must be >= 1");
+  if (n_sens < 1 || n_sens > PLH_LSQ_MAX_SENS) return fail(PLH_E_ARG, "plh_predict: n_sens must be 1 .. PLH_LSQ_MAX_SENS (8); without sensitivities use plh_resample");
+  if (n_ch < 1 || n_ch > PLH_LSQ_MAX_CHANNELS || !ch) return fail(PLH_E_ARG, "plh_predict: n_ch must be 1 .. PLH_LSQ_MAX_CHANNELS (3), with the channel array");
+  if (extrapolate != 0 && extrapolate != 1) return fail(PLH_E_ARG, "plh_predict: extrapolate must be 0 or 1");
+  if (!t || !n_pts || !run_info || !tq) return fail(PLH_E_ARG, "plh_predict: null array (only cov, group_off and status may be NULL)");
+  for (int c = 0; c < n_ch; c++) {
+    if (!ch[c].curve || !ch[c].dcurve) return fail(PLH_E_ARG, "plh_predict: a channel without curve or dcurve");
+    if (!ch[c].pred && !ch[c].dpred && !ch[c].var) return fail(PLH_E_ARG, "plh_predict: a channel without any output");
+    if (ch[c].var && !cov) return fail(PLH_E_ARG, "plh_predict: a var without cov");
+  }
+  if (group_off) { if (int rc = check_groups("plh_predict", n, n_groups, group_off)) return rc; }
+  DeviceGuard guard(m->device);
+  Stage s(m, kind, stream);
+  StreamCtx& cx = *s.cx;
+  const size_t pts = (size_t)n * max_pts, nq = (size_t)n * n_q, ns = (size_t)n_sens, n_prob = group_off ? (size_t)n_groups : (size_t)n;
+  const int width = n_ch * (1 + n_sens);
+  plpr::Args A;
+  plrs::Args& a = A.rs;
+  a.t = s.in(t, pts); a.n_pts = s.in(n_pts, (size_t)n); a.run_info = s.in(run_info, (size_t)n * n_runs);
+  for (int c = 0; c < PLH_LSQ_MAX_CHANNELS; c++) {
+    A.ch[c] = plh_predict_channel{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (c < n_ch) A.ch[c] = plh_predict_channel{s.in(ch[c].curve, pts), s.in(ch[c].dcurve, pts * ns), s.buf(ch[c].pred, nq, false), s.buf(ch[c].dpred, nq * ns, false), s.buf(ch[c].var, nq, false)};
+  }
+  A.cov = s.in(cov, n_prob * ns * ns);
+  a.status = s.buf(status, (size_t)n, false);
+  CHECK_STAGE(s);
+  if (int rc = cx.resample_tq.get(cx.st, std::vector<double>(tq, tq + n_q), &a.tq)) return rc;
+  A.group_off = nullptr; A.n_groups = group_off ? n_groups : 0;
+  if (group_off) { if (int rc = cx.group_off.get(cx.st, std::vector<int>(group_off, group_off + n_groups + 1), &A.group_off)) return rc; }
+  size_t chunk = 0;
+  if (int rc = resample_work(cx, n, n_runs, max_pts, n_q, width, 1, &chunk, &a.w)) return rc;
+  a.n_runs = n_runs; a.max_pts = max_pts; a.width = width; a.n_q = n_q; a.extrapolate = extrapolate; a.src = nullptr; a.dst = nullptr;
+  A.n_sens = n_sens; A.n_ch = n_ch;
+  for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+    a.cell0 = (int)c0; a.n_chunk = (int)std::min(chunk, (size_t)n - c0);
+    plpr::launch_chunk(s.st, A);
+  }
+  FINISH(s);
+  for (int c = 0; c < n_ch; c++) { s.back(ch[c].pred, A.ch[c].pred, nq); s.back(ch[c].dpred, A.ch[c].dpred, nq * ns); s.back(ch[c].var, A.ch[c].var, nq); }
   s.back(status, a.status, (size_t)n);
   CHECK_STAGE(s);
   return 0;

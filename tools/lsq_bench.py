@@ -16,7 +16,14 @@ dV/dtheta against differenced runs).  Writes the JSON at --out.
 
 The `channels` record, same shard and times: (a) one fused V + I call (plh_lsq_multi, two channels) against two single-channel calls plus the torch additions of their cost,
 grad and JtJ, alternating in one process, HIP events, median of --reps after one warm-up, and the difference of the two results; (b) the sensitivity kernel's own time
-(plh_last_kernel_ms) with every channel of the model requested against dV/dtheta only, the same binary, alternating --reps times."""
+(plh_last_kernel_ms) with every channel of the model requested against dV/dtheta only, the same binary, alternating --reps times.
+
+  python tools/lsq_bench.py --predict [--out profiles/predict.json]
+
+The `predict` record, same shard and times: plh_predict with all three outputs of the voltage channel (pred, dpred, var; preallocated outputs, device pointers) against
+plh_lsq_multi on the same arrays (ens.lsq: the same sweeps, sums instead of stores), alternating in one process, HIP events around --inner back-to-back calls each, median
+of --reps after a warm-up, with the spread; ens.predict (the front end: allocations and the square root for sd included) the same way; and the sensitivity kernel's own
+time of the integration that feeds them."""
 import argparse
 import copy
 import json
@@ -132,6 +139,54 @@ def measure_channels(pkg, p, n, n_q, reps):
                             "against_the_parent_build": "not measured: no build of the parent commit on the box"}}
 
 
+def measure_predict(pkg, p, n, n_q, reps, inner):
+    import torch
+    cap = pkg._capi
+    keys = [k for k in pkg.configs.SWEEP_KEYS if k in p.θ_keys]
+    cfg = pkg.configs.c4(p, n)
+    Th = torch.from_numpy(cfg["theta"]).cuda()
+    ens = pkg.simulate_ensemble(p, Th, cfg["protocol"], SOC=cfg["SOC"], device=True, max_points=cfg["max_points"], sens=keys)
+    torch.cuda.synchronize()
+    sens_ms = float(ens.kernel_ms)
+    t_end = float(ens.run_info["t_end"][:, -1].min())
+    tq = np.linspace(0.0, t_end, n_q)
+    rng = np.random.default_rng(0)
+    data = ens(tq, fields="V").V[0] + torch.from_numpy(2e-3 * rng.standard_normal(n_q)).cuda()          # cell 0's curve plus 2 mV of noise, weights 1 / sigma
+    w = torch.full((n_q,), 1.0 / 2e-3, dtype=torch.float64, device="cuda")
+    ns, mp = len(keys), ens.t.shape[1]
+    fit = ens.lsq(tq, data, weights=w)
+    cols = [p.θ_keys.index(k) for k in keys]
+    cv = pkg.fit_covariance(p, Th[:, cols].contiguous(), fit.cost, fit.grad, fit.JtJ, keys=keys)        # absolute sigma
+    lib, h = p._lib, p._h
+    pred, dpred, var = (torch.empty(*shape, dtype=torch.float64, device="cuda") for shape in ((n, n_q), (n, ns, n_q), (n, n_q)))
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    ch = (cap.PredictChannel * 1)(cap.PredictChannel(ens.V.data_ptr(), ens.dV_dtheta.data_ptr(), pred.data_ptr(), dpred.data_ptr(), var.data_ptr()))
+
+    def raw():
+        cap.check(lib, lib.plh_predict(h, n, len(ens.run_names), mp, ens.t.data_ptr(), ens.n_pts.data_ptr(), ens._run_info_raw.data_ptr(), 1, ch, ns, n_q, tq.ctypes.data, 0,
+                                       cv.cov.data_ptr(), 0, None, status.data_ptr(), cap.PLH_DEVICE, None), "plh_predict")
+
+    routes = {"plh_predict": raw, "ens_predict": lambda: ens.predict(tq, cv), "ens_lsq": lambda: ens.lsq(tq, data, weights=w)}
+    for fn in routes.values():                                                                         # warm-up: workspaces, the query grid's device copy, torch's kernels
+        fn()
+    torch.cuda.synchronize()
+    front = ens.predict(tq, cv)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(front.V, pred) and torch.equal(front.dV_dtheta, dpred) and torch.equal(torch.nan_to_num(front.V_var), torch.nan_to_num(var)))
+    ms = {nm: [] for nm in routes}
+    for _ in range(reps):                                                                              # alternating: all see the same machine
+        for nm, fn in routes.items():
+            ms[nm].append(timed(lambda: [fn() for _ in range(inner)])[0] / inner)
+    ok = (status == 0) & (cv.status == 0)
+    med = {nm: float(np.median(v)) for nm, v in ms.items()}
+    return {"cells": n, "n_q": n_q, "sens_keys": keys, "max_pts": int(mp), "calls_per_timed_window": inner, "cells_with_a_band": int(ok.sum()),
+            "front_end_has_the_raw_calls_bits": same, "sd_of_V_median_over_cells_and_times": float(torch.nanmedian(front.V_sd).cpu()),
+            "plh_predict": spread(ms["plh_predict"]), "ens_predict": spread(ms["ens_predict"]), "ens_lsq": spread(ms["ens_lsq"]),
+            "plh_predict_over_ens_lsq": med["plh_predict"] / med["ens_lsq"], "ens_predict_over_ens_lsq": med["ens_predict"] / med["ens_lsq"],
+            "sens_kernel_ms": sens_ms, "plh_predict_over_sens_kernel": med["plh_predict"] / sens_ms,
+            "bytes_written_per_call": 8 * n * n_q * (2 + ns), "bytes_to_host_without_it": 8 * n * mp * (2 + ns)}
+
+
 def fd_check(pkg, p, keys, n, n_q, window=1.0, steps=(1e-2, 1e-3, 1e-4)):
     """grad of ens.lsq against central differences of cost: two plain runs per parameter and relative step, everything at reltol = abstol = 1e-8.  A difference quotient has
     its own error -- truncation at a large step (the voltage knee at the end of the discharge is strongly curved in the parameters), the runs' integration error over the
@@ -170,20 +225,22 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--channels", action="store_true", help="the `channels` record (profiles/lsq_channels.json) instead of the plh_lsq one")
+    ap.add_argument("--predict", action="store_true", help="the `predict` record (profiles/predict.json): plh_predict against plh_lsq_multi and the sensitivity integration")
+    ap.add_argument("--inner", type=int, default=20, help="--predict: calls per timed window")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--points", type=int, default=200)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--fd-cells", type=int, default=16)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "lsq_channels.json" if a.channels else "lsq.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "predict.json" if a.predict else "lsq_channels.json" if a.channels else "lsq.json")
     import torch
     assert torch.cuda.is_available(), "lsq_bench.py needs a GPU"
     torch.cuda.init()                                      # (torch's runtime first, as in bench.py and smoke(): the library then joins the device torch opened)
     import pkgload
     pkg = pkgload.load()
     p = pkg.petlion(pkg.LCO)
-    if a.channels:
-        rec = {"channels": measure_channels(pkg, p, a.cells, a.points, a.reps)}
+    if a.channels or a.predict:
+        rec = {"predict": measure_predict(pkg, p, a.cells, a.points, a.reps, a.inner)} if a.predict else {"channels": measure_channels(pkg, p, a.cells, a.points, a.reps)}
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         json.dump(rec, open(a.out, "w"), indent=1)
         print(json.dumps(rec))
